@@ -14,6 +14,13 @@ every node of the snapshot and the selectHost of each pod.
 WORLD_SIZE, LOCAL_RANK, MASTER_ADDR/PORT set per child) before anything touches the GPU; under
 `torch.distributed.run` each process is one rank. Prints ONE JSON line on rank 0 (value = evals/s over
 all ranks, inputs resident in HBM).
+
+A plain run sets up, warms up, times the steps and prints the line. `--dump-outputs DIR` also writes what the
+last timed step computed (the per-pod top-k selectHost keys, decoded) as DIR/select_total.npy and
+DIR/select_node.npy (float64 [pods, k]; -1 where a pod has no feasible node). The inputs are seeded, so two
+builds run with the same arguments are comparable output for output. `--full` adds the legs that take runs of
+their own (N = 1): the PreFilter cycle, the one-pod-per-cycle replays and the CPU baselines, each still
+switchable with its --no-* option.
 """
 from __future__ import annotations
 
@@ -62,6 +69,13 @@ def parse():
                          "ElasticQuota; 1: the 1k x 500 CPU-harness case; 6: config 2 on a mixed cluster "
                          "(Restricted / BestEffort / CPU-bind-policy nodes, LSR pods: synth.mixed)")
     ap.add_argument("--k", type=int, default=None, help="per-pod top-k (default 3 for config 4, else 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-pod top-k result as DIR/select_total.npy and "
+                         "DIR/select_node.npy (float64 [pods, k])")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure (N = 1): PreFilter cycle, one-pod-per-cycle "
+                         "replays with their placement check, CPU baselines (see --no-cycle, --no-replay, "
+                         "--no-cpu-baseline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-replay", action="store_true")
     ap.add_argument("--no-cycle", action="store_true")
@@ -352,6 +366,18 @@ def cycle_rate(ctx, snap, pods_table, steps):
             "note": "kg_pods_upload (host columns copied into pinned staging, one async copy) + kg_eval_select + kg_result_keys per cycle"}
 
 
+def dump_outputs(path, keys):
+    """What a caller of the timed path receives, the [pods, k] selectHost keys of the last step, decoded into
+    the winning total score and node index (both exact in float64; -1 where the pod has no feasible node)."""
+    import numpy as np
+
+    from koordinator_amd import abi
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "select_total.npy"), abi.key_total(keys).astype(np.float64))
+    np.save(os.path.join(path, "select_node.npy"), abi.key_node(keys).astype(np.float64))
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "RANK" not in os.environ:
@@ -445,6 +471,8 @@ def main():
     idx = abi.key_node(keys)
     assert np.all(idx[keys != 0] < n_total)
     assert np.all(keys[:, :-1] >= keys[:, 1:])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, keys)
 
     evals = float(n_pods) * n_total * a.steps
     value = evals / elapsed
@@ -478,7 +506,7 @@ def main():
         "roofline": roofline(pmc, avg_kernel_s, n_pods * n_local, B_EVAL[config], kname),
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         if config != 5 and not a.no_cycle:
             out["cycle"] = cycle_rate(ctx, snap, pods, 10)
         if config == 5:
