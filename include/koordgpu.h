@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define KG_ABI_VERSION 12
+#define KG_ABI_VERSION 13
 
 /* LoadAware resource vector width: the default vectorizer is {cpu, memory}
  * (pkg/scheduler/plugins/loadaware/helper.go:162-173, sorted by name). */
@@ -587,6 +587,11 @@ kg_status kg_snapshot_destroy(kg_snap* snap);
 
 kg_status kg_pods_create(kg_ctx* ctx, uint32_t capacity, kg_pods** out);
 kg_status kg_pods_upload(kg_pods* pods, const kg_pod_columns* cols, uint32_t n_pods);
+/* Lanes the next plain (non config-5) kg_eval_select / kg_shard_select of this batch launches: one per pod, or one
+ * per distinct input row when the upload found equal rows and evaluating only their representatives at least halves the
+ * 64-lane waves (the duplicates' keys and status are copied from their representative on the device; results are the
+ * same). fast_lanes: the leading lanes on the float64 fast path. Either pointer may be NULL. Diagnostics only. */
+kg_status kg_pods_select_lanes(const kg_pods* pods, uint32_t* lanes, uint32_t* fast_lanes);
 kg_status kg_pods_destroy(kg_pods* pods);
 
 /* Full per-plugin Filter/Score matrix for every (pod, node) pair (the FilterPlugin/ScorePlugin

@@ -195,6 +195,9 @@ hipError_t launch_merge(const uint64_t* partial, uint32_t n_parts, uint32_t n_po
 // merge of partial rows [part0, part0 + n_parts) (row stride ld pods) for the rows list[0..n) (nullptr: 0..n)
 hipError_t launch_merge_list(const uint64_t* partial, uint32_t part0, uint32_t n_parts, uint32_t ld, const uint32_t* list,
                              uint32_t n, uint32_t k, uint64_t* out, hipStream_t s);
+// k_expand_keys: rows j of out ([n][k] keys) and pstat with rep[j] != j take row rep[j]'s (a select over the
+// representative rows only, kg_dedup.h)
+hipError_t launch_expand_keys(const uint32_t* rep, uint32_t n, uint32_t k, uint64_t* out, uint32_t* pstat, hipStream_t s);
 hipError_t launch_big_scan(const NodeRec* nodes, uint32_t n_nodes, uint32_t* big_list, uint32_t* big_count,
                            hipStream_t s);
 // Grid of the PART 2 ext kernels (special records, grid-stride): chunk and chunk count for an estimate

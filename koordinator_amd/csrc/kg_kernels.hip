@@ -394,6 +394,38 @@ __global__ __launch_bounds__(256) void k_merge(const uint64_t* __restrict__ part
     for (int t = 0; t < K; t++) out[(size_t)row * K + t] = top[t];
 }
 
+// Keys and status of the duplicate rows of a select that ran over the representative rows only (kg_dedup.h): row j
+// with rep[j] != j takes row rep[j]'s K keys and its pstat word. Readers are representatives (rep[r] == r, never
+// written here), writers are not: no ordering between threads is needed. K > 1: one 16-byte load / store per lane,
+// K / 2 lanes per row (rows of K = 4 keys are 32-byte aligned).
+template <int K>
+__global__ __launch_bounds__(256) void k_expand_keys(const uint32_t* __restrict__ rep, uint32_t n, uint64_t* out,
+                                                     uint32_t* pstat) {
+    constexpr uint32_t V = K > 1 ? 2 : 1, PER = K / V;
+    static_assert(K == 1 || K % 2 == 0, "rows are copied in 16-byte pieces");
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t j = t / PER, part = t % PER;
+    if (j >= n) return;
+    const uint32_t r = rep[j];
+    if (r == j) return;
+    if constexpr (K == 1) {
+        out[j] = out[r];
+    } else {
+        const ulonglong2* src = reinterpret_cast<const ulonglong2*>(out + (size_t)r * K) + part;
+        *(reinterpret_cast<ulonglong2*>(out + (size_t)j * K) + part) = *src;
+    }
+    if (part == 0) pstat[j] = pstat[r];
+}
+
+hipError_t launch_expand_keys(const uint32_t* rep, uint32_t n, uint32_t k, uint64_t* out, uint32_t* pstat, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (k == 1)
+        k_expand_keys<1><<<dim3((n + 255) / 256), 256, 0, s>>>(rep, n, out, pstat);
+    else
+        k_expand_keys<KG_TOPK_MAX><<<dim3((n * (KG_TOPK_MAX / 2) + 255) / 256), 256, 0, s>>>(rep, n, out, pstat);
+    return hipGetLastError();
+}
+
 // Rebuild the list of F_BIG records (after any change of node state).
 __global__ __launch_bounds__(256) void k_big_scan(const NodeRec* __restrict__ nodes, uint32_t n_nodes,
                                                   uint32_t* __restrict__ big_list, uint32_t* __restrict__ big_count) {

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/koordgpu.h"
+#include "kg_dedup.h"
 #include "kg_kernels.h"
 #include "kg_layout.h"
 
@@ -200,6 +201,12 @@ struct kg_pods {
     PodsDev dev{};
     uint32_t* d_order = nullptr;  // lanes of the base select: fast pods grouped by wave kind, then integer-path pods
     uint32_t n_fast = 0;          // pods in the float64 fast domain (the leading d_order entries)
+    // plain select of one representative per distinct input row (kg_dedup.h); set by every upload
+    uint32_t* d_rep = nullptr;     // per pod the lowest row equal to it (valid when dedup)
+    uint32_t* d_rorder = nullptr;  // d_order restricted to the representatives
+    uint32_t n_rep = 0, n_rep_fast = 0;
+    bool dedup = false;            // the batch has rep / rorder (no config-5 columns, no KG_POD_RSV_REQUIRED pod)
+    std::vector<uint32_t> dedup_slots;  // dedup_rows scratch
     uint32_t* d_pmap = nullptr;   // config-5 "plain" pods (batch positions) grouped by wave kind
     uint32_t* d_xlist = nullptr;  // config-5 pods through k_ext_select (batch positions)
     uint32_t* d_xpos = nullptr;   // per pod its lane in d_xlist (~0 = a plain pod): the stored pairs' column
@@ -1296,7 +1303,7 @@ namespace {
 // first; the config-5 regions after `ext` are copied only when the batch carries config-5 data (else they
 // are set on the device). The layout depends on n only, so cached replay graphs keyed on n stay valid.
 struct PodLayout {
-    size_t cols, flags, order, pmap, ext, xlist, xpos, stat, dev_req, dev_bw, xcols, dclass, dcls, total;
+    size_t cols, flags, order, pmap, rep, rorder, ext, xlist, xpos, stat, dev_req, dev_bw, xcols, dclass, dcls, total;
 };
 
 PodLayout pod_layout(uint32_t n) {
@@ -1311,6 +1318,8 @@ PodLayout pod_layout(uint32_t n) {
     L.flags = take(sizeof(uint32_t) * (size_t)n);
     L.order = take(sizeof(uint32_t) * (size_t)n);
     L.pmap = take(sizeof(uint32_t) * (size_t)n);
+    L.rep = take(sizeof(uint32_t) * (size_t)n);
+    L.rorder = take(sizeof(uint32_t) * (size_t)n);
     L.ext = o;
     L.xlist = take(sizeof(uint32_t) * (size_t)n);
     L.xpos = take(sizeof(uint32_t) * (size_t)n);
@@ -1342,6 +1351,8 @@ void pod_views(kg_pods* p, uint32_t n) {
     v.flags = reinterpret_cast<uint32_t*>(d + L.flags);
     p->d_order = reinterpret_cast<uint32_t*>(d + L.order);
     p->d_pmap = reinterpret_cast<uint32_t*>(d + L.pmap);
+    p->d_rep = reinterpret_cast<uint32_t*>(d + L.rep);
+    p->d_rorder = reinterpret_cast<uint32_t*>(d + L.rorder);
     p->d_xlist = reinterpret_cast<uint32_t*>(d + L.xlist);
     p->d_xpos = reinterpret_cast<uint32_t*>(d + L.xpos);
     p->d_stat_list = reinterpret_cast<uint32_t*>(d + L.stat);
@@ -1500,6 +1511,8 @@ kg_status kg_pods_upload(kg_pods* p, const kg_pod_columns* cols, uint32_t n) {
     uint32_t* xlist = reinterpret_cast<uint32_t*>(h + L.xlist);
     uint32_t* stat = reinterpret_cast<uint32_t*>(h + L.stat);
     uint32_t np = 0, nx = 0, ns = 0;
+    uint32_t n_rep = n, n_rep_fast = n_fast;
+    bool dedup = false;
     std::vector<DevClass> classes;
     bool unclassed = false;
     if (!ext_cols && !any_rsv_req) {
@@ -1573,6 +1586,18 @@ kg_status kg_pods_upload(kg_pods* p, const kg_pod_columns* cols, uint32_t n) {
         std::memcpy(pmap, by.data(), sizeof(uint32_t) * np);
         if (!classes.empty()) std::memcpy(h + L.dclass, classes.data(), sizeof(DevClass) * classes.size());
     }
+    // representative rows for the plain select (select_local on a snapshot without config-5 tables reads the nine
+    // columns and the flags word only): when no pod carries config-5 content (no GPU request, no reservation class, no
+    // KG_POD_RSV_REQUIRED; the bindings pass the config-5 columns with their defaults), so config-5 batches pay nothing
+    if (np == n) {
+        DedupRows rows{};
+        for (int c = 0; c < DEDUP_COLS; c++) rows.col[c] = hc + (size_t)c * n;
+        rows.flags = f;
+        uint32_t* rp = reinterpret_cast<uint32_t*>(h + L.rep);
+        dedup_rows(rows, n, rp, p->dedup_slots);
+        dedup_order(order, n, n_fast, rp, reinterpret_cast<uint32_t*>(h + L.rorder), &n_rep_fast, &n_rep);
+        dedup = true;
+    }
     uint32_t n_stat_cls = 0;
     while (n_stat_cls < ns && xc[stat[n_stat_cls]] == 0) n_stat_cls++;
     // ---- one copy of the regions this batch needs; absent config-5 columns set on the device
@@ -1598,6 +1623,9 @@ kg_status kg_pods_upload(kg_pods* p, const kg_pod_columns* cols, uint32_t n) {
     // ---- commit
     p->n = n;
     p->n_fast = n_fast;
+    p->n_rep = n_rep;
+    p->n_rep_fast = n_rep_fast;
+    p->dedup = dedup;
     p->fast_ok = n_fast == n;
     p->pod_policy = any_pol;
     p->any_cpu_bind = any_bind;
@@ -2090,6 +2118,16 @@ static LaunchSelect make_select(const kg_snap* s, const PodsDev& pods, const uin
     return a;
 }
 
+// The plain select runs one lane per distinct input row (kg_pods_upload: rep / rorder) when the reduced lists have at
+// most half the 64-lane waves of the full ones; otherwise (and with KG_NO_POD_DEDUP set: A/B aid, read per call) the
+// launch is the full one and no expansion follows. The threshold is the measured break-even of the extra k_expand_keys
+// launch (tools/dedup_ab.py --breakeven on config 2's nodes): 5 -> 4 and 5 -> 3 waves and 40 -> 39 .. 36
+// cost up to 4 % or were even, 40 -> 32 gained 2.5 %, 40 -> 24 12 %, 5 -> 1 11 %; at half the waves no case lost.
+static bool dedup_on(const kg_pods* p) {
+    if (!p->dedup || std::getenv("KG_NO_POD_DEDUP")) return false;
+    return 2 * dedup_waves(p->n_rep, p->n_rep_fast) <= dedup_waves(p->n, p->n_fast);
+}
+
 // The plain pods' select can run beside the config-5 kernels when it is the fused top-1 (no partials shared
 // with the x lanes' merge).
 static bool plain_side_ok(const kg_snap* s, const kg_pods* p, uint32_t kk) {
@@ -2325,7 +2363,10 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     }
     // per pod: fast lanes (float64 fast path + F_BIG records on the integer path), then the integer lanes
     uint32_t parts = 0;
-    LaunchSelect a = make_select(s, p->dev, p->d_order, p->n, p->n_fast, p->n, kk, true, d_out, nullptr, p->d_pstat, &parts);
+    // one lane per distinct input row when that saves waves (dedup_on); k_expand_keys then serves the duplicates
+    const bool dd = dedup_on(p);
+    LaunchSelect a = make_select(s, p->dev, dd ? p->d_rorder : p->d_order, dd ? p->n_rep : p->n,
+                                 dd ? p->n_rep_fast : p->n_fast, p->n, kk, true, d_out, nullptr, p->d_pstat, &parts);
     kg_status st = ensure_partial(p, std::max<size_t>((size_t)parts * p->n * kk, 1));
     if (st != KG_OK) return st;
     a.partial = p->d_partial;
@@ -2351,7 +2392,12 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         a.iseg_cap = (uint32_t)(p->ipairs_cap / (256 * 64) + 1);
         a.iseed = 256;
     }
-    if (!std::getenv("KG_NO_SIDE_STREAM")) {
+    // a deduplicated launch of one pod block of fast lanes keeps the class-1 select on the main stream: the fork / join
+    // around kernels of ~25 us costs more than running them in turn (config 2: 0.072 -> 0.067 ms per step).
+    // Keyed on dd, not on the launch shape, on purpose: with the gate off (or KG_NO_POD_DEDUP, which so changes the
+    // stream placement along with the lane count) the launch stays exactly the parent's
+    const bool c1_main = dd && n_int == 0 && a.n_fast <= 256;
+    if (!std::getenv("KG_NO_SIDE_STREAM") && !c1_main) {
         // beside the fast lanes' kernels: the pruned integer lanes (disjoint rows of out) or, without them, the
         // fused top-1 select of storage class 1 (atomicMax into the same rows)
         st = ensure_side(ctx);
@@ -2368,6 +2414,8 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     // later on ctx->stream (an upload into the pod columns, a free) can overtake them
     if (le != hipSuccess && a.side) hipStreamSynchronize(a.side);
     HIP_TRY(ctx, le);
+    // after the side-stream join: every consumer (kg_result_keys, the all-gather, kg_result_status) sees whole tables
+    if (dd) HIP_TRY(ctx, launch_expand_keys(p->d_rep, p->n, kk, d_out, p->d_pstat, ctx->stream));
     return record_end(ctx, e0, e1);
 }
 
@@ -2395,6 +2443,15 @@ kg_status kg_result_keys(kg_pods* p, uint64_t* out) {
     }
     for (uint32_t j = 0; j < p->n; j++)
         for (uint32_t t = 0; t < p->k_last; t++) out[(size_t)j * p->k_last + t] = h[(size_t)j * p->kk_last + t];
+    return KG_OK;
+}
+
+kg_status kg_pods_select_lanes(const kg_pods* p, uint32_t* lanes, uint32_t* fast_lanes) {
+    if (!p) return KG_INVALID_ARG;
+    std::lock_guard<std::mutex> g(p->ctx->mu);
+    const bool dd = dedup_on(p);
+    if (lanes) *lanes = dd ? p->n_rep : p->n;
+    if (fast_lanes) *fast_lanes = dd ? p->n_rep_fast : p->n_fast;
     return KG_OK;
 }
 

@@ -73,6 +73,8 @@ def lib():
     L.kg_pods_create.restype = st
     L.kg_pods_upload.argtypes = [vp, P(abi.KgPodColumns), u32]
     L.kg_pods_upload.restype = st
+    L.kg_pods_select_lanes.argtypes = [vp, P(u32), P(u32)]
+    L.kg_pods_select_lanes.restype = st
     L.kg_pods_destroy.argtypes = [vp]
     L.kg_pods_destroy.restype = st
     L.kg_eval_verify.argtypes = [vp, vp, P(abi.KgVerifyOut)]
@@ -353,6 +355,13 @@ class PodBatch:
             cols = abi.pod_columns(pods)
             self._cols, self._cols_key = cols, (pods, tuple(pods.values()))
         self.ctx.check(self.ctx.L.kg_pods_upload(self.h, C.byref(cols), self.n), "kg_pods_upload")
+
+    def select_lanes(self):
+        """kg_pods_select_lanes: (lanes, fast lanes) the next plain select launches (fewer than n when equal rows share
+        one evaluation)."""
+        lanes, fast = C.c_uint32(), C.c_uint32()
+        self.ctx.check(self.ctx.L.kg_pods_select_lanes(self.h, C.byref(lanes), C.byref(fast)), "kg_pods_select_lanes")
+        return lanes.value, fast.value
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
