@@ -4,6 +4,9 @@
 //              (each record's 256-byte fast block arrives by wide scalar loads into SGPRs), running
 //              top-K per lane; per-(chunk, pod) partial keys. Specialised per node storage class
 //              (records are stored grouped by class) and per enabled-plugin set.
+//   k_select_small / k_small_finish  the fused top-1 select of at most 256 fast lanes: both storage classes and
+//              the F_BIG records in one launch, per-chunk slots instead of atomics, then one merge-and-expand launch
+//              that writes every row (no memset, no k_big_sel, no k_expand_keys).
 //   k_big_sel  the nodes outside the float64 fast path (F_BIG records) for the fast lanes, on the
 //              integer path, chunked over the device's F_BIG list.
 //   k_merge    per pod: top-K over partial keys (global selectHost of one shard or of the
@@ -302,6 +305,199 @@ __global__ __launch_bounds__(256) KG_SEL1_ATTR void k_select1(const NodeRec* __r
     else
         top = select1_loop<PM, CLS, FK_ANY>(nodes, zones, lo, hi, index_base, cv, pf);
     if (live && top) atomicMax((unsigned long long*)(out + o), (unsigned long long)top);
+}
+
+// One-pod-block fused top-1 select (LaunchSelect.small): both storage classes and the F_BIG records in one launch,
+// no atomics and nothing to zero. grid (1, nc1 + nc0): workgroups [0, nc1) take class-1 chunks of chunk1 records (the
+// zone walk makes them the dearer ones: they start first), the others class-0 chunks of chunk0; at most 64 records
+// per chunk. A block is `slices` copies of the fast lanes rounded up to whole waves (lp): slice s walks the s-th part
+// of the chunk, so a compute unit holds several waves per SIMD that hide each other's record loads (one wave per SIMD
+// spends three quarters of its time waiting for them); the slices' results meet in LDS. Slice 0 stores
+// every lane's best key of the chunk and its status pair (below) into slot [chunk][lane] of skeys / sub / sfhi (idle
+// lanes: zeros): every slot is written by every launch, and k_small_finish merges them. The fast records go through
+// select1_loop (the arithmetic of k_select1); the F_BIG records of the slice's part (flagged on the record, so the
+// branch is wave-uniform; the device's F_BIG list is not read) follow on the integer path, with k_big_sel's
+// NodeResourcesFit / LoadAware bound prune against the lane's best key so far: a floor below the pod's final key, so no
+// record that could win is skipped. Keys hold the inverted node index: the maximum does not depend on the order of
+// evaluation. The slice index is read from the wave's first lane, so that the compiler sees the record range as
+// wave-uniform and select1_loop keeps its wide scalar record loads. WG: the launch bound, 512 (up to 256 VGPRs: the
+// inline integer path fits without scratch) or 1024 (128 VGPRs: it spills; more copies per workgroup). The chunks are
+// dealt to the XCDs in contiguous runs (xcd_block; launch order measured the same).
+template <uint32_t PM, uint32_t WG>
+__global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__ nodes, const ZoneRec* __restrict__ zones,
+                                                           PodsDev pods, uint32_t n_lanes, uint32_t lp, uint32_t n0,
+                                                           uint32_t n_end, uint32_t chunk0, uint32_t chunk1, uint32_t nc1,
+                                                           uint32_t index_base, KCfg cfg, uint64_t* __restrict__ skeys,
+                                                           uint32_t* __restrict__ sub, uint32_t* __restrict__ sfhi,
+                                                           const uint32_t* __restrict__ order) {
+    __shared__ uint64_t lk[WG];
+    __shared__ uint2 ls[WG];
+    const uint32_t c = xcd_block().y, slices = blockDim.x / lp;
+    const uint32_t j = threadIdx.x % lp;
+    const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / lp));  // lp is whole waves
+    const bool live = j < n_lanes;
+    const uint32_t row = live ? (order ? order[j] : j) : 0u;
+    const PodV p = load_pod(pods, row);
+    const bool cls1 = c < nc1;  // uniform
+    const uint32_t wlo = cls1 ? n0 + c * chunk1 : (c - nc1) * chunk0;
+    const uint32_t whi = cls1 ? min(n_end, wlo + chunk1) : min(n0, wlo + chunk0);
+    // the chunk's F_BIG records as a wave-uniform mask (lane t of every wave looks at record wlo + t)
+    const uint32_t t = threadIdx.x & 63u;
+    bool big = false;
+    if (wlo + t < whi) big = ((uint32_t)nodes[wlo + t].v[N_FLAGS] & F_BIG) != 0;
+    uint64_t bigm = __ballot(big);
+    const PodF pf = to_podf(p, cfg);
+    const KCfg cv = cfg_in_vgprs(cfg);
+    const bool prod = __all(!live || fast_kind_match(FK_PROD, p)), batch = __all(!live || fast_kind_match(FK_BATCH, p));
+    const uint32_t span = (whi - wlo + slices - 1) / slices;
+    const uint32_t lo = min(whi, wlo + sl * span), hi = min(whi, lo + span);
+    uint64_t top;
+    if (!cls1) {
+        if (prod) top = select1_loop<PM, 0, FK_PROD>(nodes, zones, lo, hi, index_base, cv, pf);
+        else if (batch) top = select1_loop<PM, 0, FK_BATCH>(nodes, zones, lo, hi, index_base, cv, pf);
+        else top = select1_loop<PM, 0, FK_ANY>(nodes, zones, lo, hi, index_base, cv, pf);
+    } else {
+        if (prod) top = select1_loop<PM, 1, FK_PROD>(nodes, zones, lo, hi, index_base, cv, pf);
+        else if (batch) top = select1_loop<PM, 1, FK_BATCH>(nodes, zones, lo, hi, index_base, cv, pf);
+        else top = select1_loop<PM, 1, FK_ANY>(nodes, zones, lo, hi, index_base, cv, pf);
+    }
+    // the slice's bits of the mask: records [lo, hi)
+    bigm = lo < whi ? bigm >> (lo - wlo) : 0ull;
+    if (hi - lo < 64u) bigm &= (1ull << (hi - lo)) - 1ull;
+    // status as k_big_sel would set it behind the fast records' kernels: there a pair is evaluated (and its
+    // KG_ST_UNSUPPORTED seen) when its bound reaches the pod's best key over ALL fast records. The prune here uses the
+    // best fast key of this part only (lower: a superset is evaluated), and keeps what the finish needs to decide as
+    // k_big_sel does: the high word of that fast key and, over the pairs found KG_ST_UNSUPPORTED, the highest bound
+    // (high word + 1; 0xFFFFFFFF for an F_VBIG record, which is never pruned)
+    const uint32_t fhi = (uint32_t)(top >> 32);
+    const uint64_t floor_key = top;
+    uint32_t ub = 0;
+    while (bigm) {
+        const uint32_t i = lo + (uint32_t)__ffsll((unsigned long long)bigm) - 1u;
+        bigm &= bigm - 1;
+        const int64_t* nv = nodes[i].v;
+        bool need = live;
+        uint32_t bhi = 0xFFFFFFFFu;
+        if (!((uint32_t)nv[N_FLAGS] & F_VBIG)) {
+            const FastRec& fr = *reinterpret_cast<const FastRec*>(&nv[FAST_BEGIN]);
+            uint32_t part = 0;
+            const bool ok = fast_eval<KG_PLUGIN_NRF | KG_PLUGIN_LA, 0>(cv, fr, zones + i, pf, part);
+            const uint32_t b = part + (uint32_t)cfg.w_numa * 100u;
+            const uint64_t bound = ((uint64_t)b << 32) | 0xFFFFFFFFull;
+            need = need && ok && bound >= floor_key;
+            bhi = min(b, 0xFFFFFFFDu) + 1u;
+        }
+        if (need) {
+            const PairOut o = eval_pair<false, false, true, true, false>(cfg, nv, zones + i, p);
+            if (o.status & KG_ST_UNSUPPORTED) ub = max(ub, bhi);
+            const uint64_t key = pair_key(cfg, o, rec_gidx(nodes[i], index_base));
+            top = key > top ? key : top;
+        }
+    }
+    uint2 st = make_uint2(fhi, ub);
+    if (slices > 1) {  // uniform
+        lk[threadIdx.x] = top;
+        ls[threadIdx.x] = st;
+        __syncthreads();
+        if (sl != 0) return;
+        for (uint32_t s2 = 1; s2 < slices; s2++) {
+            const uint64_t k2 = lk[s2 * lp + j];
+            const uint2 t2 = ls[s2 * lp + j];
+            st.x = max(st.x, t2.x);
+            st.y = max(st.y, t2.y);
+            top = k2 > top ? k2 : top;
+        }
+    }
+    const size_t slot = (size_t)c * lp + j;
+    skeys[slot] = live ? top : 0ull;
+    sfhi[slot] = live ? st.x : 0u;
+    sub[slot] = live ? st.y : 0u;
+}
+
+// Second and last launch of the one-pod-block select: per row j of [0, n) the maximum key and the status over the
+// n_chunks slots of its lane, lane_of[j] (the lane of the row's representative under the pod-row reduction, else of
+// the row itself), plain-stored to out[j] / pstat[j]: every row is written, so neither table is zeroed beforehand, and
+// the duplicates need no expansion launch. A workgroup serves 1024 rows: its threads first merge every lane (threads =
+// lanes x slices of the chunks, sixteen independent loads in flight per thread: one load per step makes the merge a
+// chain of L2 round trips; then over the slices in LDS), then each takes a row. Status: KG_ST_UNSUPPORTED when some
+// unsupported pair's bound (sub) reaches the lane's best fast key (sfhi, read only when the lane has such a pair).
+constexpr uint32_t SMALL_FIN_WG = 1024;
+// Maxima over the chunk slots c = sl, sl + slices, ... of one lane: sixteen slots in flight at a time (indices past the
+// end repeat the last slot, which changes no maximum).
+template <typename T>
+__device__ __forceinline__ T small_merge(const T* __restrict__ slots, uint32_t n_chunks, uint32_t lp, uint32_t lane,
+                                         uint32_t sl, uint32_t slices) {
+    constexpr uint32_t U = 16;
+    T best = 0;
+    for (uint32_t c = sl; c < n_chunks; c += slices * U) {
+        T v[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++) v[u] = slots[(size_t)min(c + u * slices, n_chunks - 1u) * lp + lane];
+#pragma unroll
+        for (uint32_t u = 0; u < U; u++) best = v[u] > best ? v[u] : best;
+    }
+    return best;
+}
+
+template <typename T>
+__device__ __forceinline__ T small_fold(T* lds, T v, uint32_t lp, uint32_t slices) {
+    // lds[threadIdx.x] of every slice -> the lane's value in lds[lane] (lane < lp)
+    lds[threadIdx.x] = v;
+    __syncthreads();
+    if (threadIdx.x < lp) {
+        for (uint32_t s2 = 1; s2 < slices; s2++) {
+            const T w = lds[s2 * lp + threadIdx.x];
+            v = w > v ? w : v;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < lp) lds[threadIdx.x] = v;
+    __syncthreads();
+    return v;
+}
+
+__global__ __launch_bounds__(SMALL_FIN_WG) void k_small_finish(const uint64_t* __restrict__ skeys,
+                                                               const uint32_t* __restrict__ sub,
+                                                               const uint32_t* __restrict__ sfhi, uint32_t n_chunks,
+                                                               uint32_t lp, uint32_t n_lanes,
+                                                               const uint8_t* __restrict__ lane_of, uint32_t n,
+                                                               uint64_t* __restrict__ out, uint32_t* __restrict__ pstat) {
+    __shared__ uint64_t mk[SMALL_FIN_WG];
+    __shared__ uint32_t mu[SMALL_FIN_WG], mf[SMALL_FIN_WG];
+    const uint32_t slices = SMALL_FIN_WG / lp;  // lp = 64, 128, 192 or 256
+    const uint32_t lane = threadIdx.x % lp, sl = threadIdx.x / lp;
+    const bool on = sl < slices && lane < n_lanes;
+    uint64_t key = 0;
+    uint32_t ub0 = 0;
+    if (on) {  // as small_merge, both tables' loads in flight together
+        constexpr uint32_t U = 16;
+        for (uint32_t c = sl; c < n_chunks; c += slices * U) {
+            uint64_t kv[U];
+            uint32_t uv[U];
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) {
+                const size_t at = (size_t)min(c + u * slices, n_chunks - 1u) * lp + lane;
+                kv[u] = skeys[at];
+                uv[u] = sub[at];
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) {
+                key = kv[u] > key ? kv[u] : key;
+                ub0 = max(ub0, uv[u]);
+            }
+        }
+    }
+    small_fold(mk, key, lp, slices);
+    const uint32_t ub = small_fold(mu, ub0, lp, slices);
+    // rare: some lane met an unsupported pair
+    if (__syncthreads_or(threadIdx.x < lp && ub != 0u))
+        small_fold(mf, on ? small_merge(sfhi, n_chunks, lp, lane, sl, slices) : 0u, lp, slices);
+    const uint32_t r = blockIdx.x * SMALL_FIN_WG + threadIdx.x;
+    if (r < n) {
+        const uint32_t l = lane_of[r];
+        out[r] = mk[l];
+        pstat[r] = mu[l] != 0u && mu[l] > mf[l] ? KG_ST_UNSUPPORTED : 0u;
+    }
 }
 
 // The F_BIG records (integer path) for the fast lanes: lane = pod (via order), blockIdx.y = chunk of the
@@ -1068,7 +1264,46 @@ static void select_fast(const LaunchSelect& a, const SelectRange& r, hipStream_t
     }
 }
 
+// LaunchSelect.small: k_select_small over both classes' chunks, then k_small_finish over the rows
+static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
+    const uint32_t lp = (a.n_fast + 63) / 64 * 64;
+    const SelectRange &r0 = a.range[0], &r1 = a.range[1];
+    const uint32_t nc = r0.n_chunks + r1.n_chunks;
+    if (a.k != 1 || !a.fused || a.n_fast == 0 || a.n_fast != a.n_pods || lp > 256 || nc == 0 || nc > SMALL_MAX_CHUNKS ||
+        (r0.n_chunks && (r0.chunk == 0 || r0.chunk > SMALL_MAX_CHUNK)) ||
+        (r1.n_chunks && (r1.chunk == 0 || r1.chunk > SMALL_MAX_CHUNK)) || a.small_slices == 0 ||
+        a.small_slices * lp > SMALL_WG || !a.skeys || !a.sub || !a.sfhi || !a.lane_of)
+        return hipErrorInvalidValue;
+    dim3 grid(1, nc), block(lp * a.small_slices);
+#define KG_SMALL(PMV)                                                                                                 \
+    do {                                                                                                              \
+        if (block.x <= 512u)                                                                                          \
+            k_select_small<PMV, 512><<<grid, block, 0, s>>>(a.nodes, a.zones, a.pods, a.n_fast, lp, r0.end, r1.end,   \
+                                                            r0.chunk, r1.chunk, r1.n_chunks, a.index_base, a.cfg,     \
+                                                            a.skeys, a.sub, a.sfhi, a.order);                         \
+        else                                                                                                          \
+            k_select_small<PMV, 1024><<<grid, block, 0, s>>>(a.nodes, a.zones, a.pods, a.n_fast, lp, r0.end, r1.end,  \
+                                                             r0.chunk, r1.chunk, r1.n_chunks, a.index_base, a.cfg,    \
+                                                             a.skeys, a.sub, a.sfhi, a.order);                        \
+    } while (0)
+    switch (a.cfg.plugins & 7u) {
+        case 0: KG_SMALL(0); break;
+        case 1: KG_SMALL(1); break;
+        case 2: KG_SMALL(2); break;
+        case 3: KG_SMALL(3); break;
+        case 4: KG_SMALL(4); break;
+        case 5: KG_SMALL(5); break;
+        case 6: KG_SMALL(6); break;
+        default: KG_SMALL(7); break;
+    }
+#undef KG_SMALL
+    k_small_finish<<<dim3((a.n_rows + SMALL_FIN_WG - 1) / SMALL_FIN_WG), SMALL_FIN_WG, 0, s>>>(
+        a.skeys, a.sub, a.sfhi, nc, lp, a.n_fast, a.lane_of, a.n_rows, a.out, a.pstat);
+    return KG_LAUNCH_CHECK();
+}
+
 hipError_t launch_select(const LaunchSelect& a, hipStream_t s) {
+    if (a.small) return launch_select_small(a, s);
     const uint32_t K = a.k == 1 ? 1u : (uint32_t)KG_TOPK_MAX;
     const uint32_t n_fast = a.fast ? a.n_fast : 0u, n_int = a.n_pods - n_fast;
     // K == 1: the fused fast path and the integer lanes update out[row] by atomicMax; K > 1 fused: every lane

@@ -43,6 +43,7 @@ struct kg_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
     double prof_ms = 0.0;
     uint64_t prof_launches = 0;
+    int cus = -1;  // compute units of the device (device_cus), queried on first use
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
     // config-5 select: the plain pods' k_select1 runs on `side` while `stream` builds DevSum and pass 1
@@ -204,6 +205,10 @@ struct kg_pods {
     // plain select of one representative per distinct input row (kg_dedup.h); set by every upload
     uint32_t* d_rep = nullptr;     // per pod the lowest row equal to it (valid when dedup)
     uint32_t* d_rorder = nullptr;  // d_order restricted to the representatives
+    // per row the lane of d_order / (under dedup, through rep) of d_rorder that serves it, for the one-pod-block
+    // select's finish (k_small_finish); filled when the list has at most 256 lanes
+    uint8_t* d_lane = nullptr;
+    uint8_t* d_rlane = nullptr;
     uint32_t n_rep = 0, n_rep_fast = 0;
     bool dedup = false;            // the batch has rep / rorder (no config-5 columns, no KG_POD_RSV_REQUIRED pod)
     std::vector<uint32_t> dedup_slots;  // dedup_rows scratch
@@ -1303,7 +1308,7 @@ namespace {
 // first; the config-5 regions after `ext` are copied only when the batch carries config-5 data (else they
 // are set on the device). The layout depends on n only, so cached replay graphs keyed on n stay valid.
 struct PodLayout {
-    size_t cols, flags, order, pmap, rep, rorder, ext, xlist, xpos, stat, dev_req, dev_bw, xcols, dclass, dcls, total;
+    size_t cols, flags, order, pmap, rep, rorder, lane, rlane, ext, xlist, xpos, stat, dev_req, dev_bw, xcols, dclass, dcls, total;
 };
 
 PodLayout pod_layout(uint32_t n) {
@@ -1320,6 +1325,8 @@ PodLayout pod_layout(uint32_t n) {
     L.pmap = take(sizeof(uint32_t) * (size_t)n);
     L.rep = take(sizeof(uint32_t) * (size_t)n);
     L.rorder = take(sizeof(uint32_t) * (size_t)n);
+    L.lane = take((size_t)n);
+    L.rlane = take((size_t)n);
     L.ext = o;
     L.xlist = take(sizeof(uint32_t) * (size_t)n);
     L.xpos = take(sizeof(uint32_t) * (size_t)n);
@@ -1353,6 +1360,8 @@ void pod_views(kg_pods* p, uint32_t n) {
     p->d_pmap = reinterpret_cast<uint32_t*>(d + L.pmap);
     p->d_rep = reinterpret_cast<uint32_t*>(d + L.rep);
     p->d_rorder = reinterpret_cast<uint32_t*>(d + L.rorder);
+    p->d_lane = d + L.lane;
+    p->d_rlane = d + L.rlane;
     p->d_xlist = reinterpret_cast<uint32_t*>(d + L.xlist);
     p->d_xpos = reinterpret_cast<uint32_t*>(d + L.xpos);
     p->d_stat_list = reinterpret_cast<uint32_t*>(d + L.stat);
@@ -1597,6 +1606,17 @@ kg_status kg_pods_upload(kg_pods* p, const kg_pod_columns* cols, uint32_t n) {
         dedup_rows(rows, n, rp, p->dedup_slots);
         dedup_order(order, n, n_fast, rp, reinterpret_cast<uint32_t*>(h + L.rorder), &n_rep_fast, &n_rep);
         dedup = true;
+    }
+    // row -> lane for the one-pod-block select (select_small): the lists of at most 256 lanes
+    if (n <= 256)
+        for (uint32_t t = 0; t < n; t++) h[L.lane + order[t]] = (uint8_t)t;
+    if (dedup && n_rep <= 256) {
+        const uint32_t* rp = reinterpret_cast<const uint32_t*>(h + L.rep);
+        const uint32_t* ro = reinterpret_cast<const uint32_t*>(h + L.rorder);
+        uint8_t* rl = h + L.rlane;
+        for (uint32_t t = 0; t < n_rep; t++) rl[ro[t]] = (uint8_t)t;
+        for (uint32_t j = 0; j < n; j++)  // rep[j] <= j: a representative's lane is set before its duplicates read it
+            if (rp[j] != j) rl[j] = rl[rp[j]];
     }
     uint32_t n_stat_cls = 0;
     while (n_stat_cls < ns && xc[stat[n_stat_cls]] == 0) n_stat_cls++;
@@ -2307,6 +2327,66 @@ static kg_status ext_select_local(kg_snap* s, kg_pods* p, uint32_t kk, uint64_t*
     return KG_OK;
 }
 
+// Compute units of the context's device, queried once per context (0 when the query fails).
+static uint32_t device_cus(kg_ctx* ctx) {
+    if (ctx->cus < 0 && hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess)
+        ctx->cus = 0;
+    return ctx->cus > 0 ? (uint32_t)ctx->cus : 0u;
+}
+
+// The one-pod-block fused top-1 select (k_select_small + k_small_finish, kg_kernels.hip): top-1, fused,
+// every lane a fast lane and at most 256 of them, with or without the pod-row reduction. Sets a's geometry for it. A
+// workgroup holds SMALL_COPIES_* copies of the lanes and, with its registers, has a compute unit to itself, so the
+// launch is fastest as one round of workgroups: the chunk lengths are derived from the class lengths so that the
+// chunks number about SMALL_FILL of the device's compute units, a class-1 record counting as 4/3 of a class-0 one
+// (its chunks are 3/4 as long); between SMALL_MIN_CHUNK and SMALL_MAX_CHUNK records, so a large snapshot runs several
+// rounds, and one that needs more than SMALL_MAX_CHUNKS chunks keeps the general path. KG_NO_SMALL_SELECT (read per
+// call) keeps the general path too; KG_SMALL_CHUNKS="c0,c1,copies" sets the geometry (measurement aid).
+// threads that the copies of the lanes may fill (512: the launch-bound variant without scratch; 1024: the spilling one)
+constexpr uint32_t SMALL_COPIES_WG = 1024, SMALL_BIG_DEN = 250;
+constexpr uint32_t SMALL_MIN_CHUNK = 8, SMALL_FILL_NUM = 7, SMALL_FILL_DEN = 8;
+static bool select_small(const kg_snap* s, LaunchSelect& a) {
+    if (a.k != 1 || !a.fused || a.n_fast == 0 || a.n_fast != a.n_pods || a.n_fast > 256) return false;
+    if (std::getenv("KG_NO_SMALL_SELECT")) return false;
+    // F_BIG gate: the F_BIG records run inline on the integer path behind the fast records of the wave that meets
+    // them, pruned by that wave's best fast key only, and the launch ends with its slowest workgroup; k_big_sel spreads
+    // them over the chip and prunes with the final key. Measured (tools/small_select_ab.py --shares; this
+    // path / the general one, ms): 0.2 % F_BIG records 0.048 / 0.066, 0.4 % 0.054 / 0.068, 0.6 % 0.075 / 0.071, 1 %
+    // 0.075 / 0.075, 15 % 0.096 / 0.079. The break-even lies between 0.4 % and 0.6 %: the path is taken up to 1 record
+    // in SMALL_BIG_DEN (count at the last upload / row update; records that turn F_BIG on the device later are still
+    // evaluated). KG_SMALL_ALLOW_BIG (read per call) lifts the gate: the A/B tool and the tests
+    if ((uint64_t)s->n_big_est * SMALL_BIG_DEN > s->n && !std::getenv("KG_SMALL_ALLOW_BIG")) return false;
+    const uint32_t lp = (a.n_fast + 63) / 64 * 64;
+    const uint32_t len0 = a.range[0].end - a.range[0].begin, len1 = a.range[1].end - a.range[1].begin;
+    const uint32_t cus = std::max<uint32_t>(device_cus(s->ctx), 8u);
+    const uint32_t want = std::max<uint32_t>(1u, cus * SMALL_FILL_NUM / SMALL_FILL_DEN);
+    const uint64_t work = (uint64_t)len0 * 3 + (uint64_t)len1 * 4;  // in thirds of a class-0 record
+    uint32_t chunk[2];
+    chunk[0] = (uint32_t)std::min<uint64_t>(SMALL_MAX_CHUNK, std::max<uint64_t>(SMALL_MIN_CHUNK, (work + 3ull * want - 1) / (3ull * want)));
+    chunk[1] = std::max<uint32_t>(1u, chunk[0] * 3 / 4);
+    a.small_slices = SMALL_COPIES_WG / lp;
+    if (const char* e = std::getenv("KG_SMALL_CHUNKS")) {
+        unsigned c0 = 0, c1 = 0, sl = 0;
+        if (std::sscanf(e, "%u,%u,%u", &c0, &c1, &sl) == 3 && c0 >= 1 && c0 <= SMALL_MAX_CHUNK && c1 >= 1 &&
+            c1 <= SMALL_MAX_CHUNK && sl >= 1 && sl * lp <= SMALL_WG) {
+            chunk[0] = c0;
+            chunk[1] = c1;
+            a.small_slices = sl;
+        }
+    }
+    SelectRange r[2] = {a.range[0], a.range[1]};
+    for (int c = 0; c < 2; c++) {
+        r[c].chunk = chunk[c];
+        r[c].n_chunks = (r[c].end - r[c].begin + chunk[c] - 1) / chunk[c];
+        r[c].part0 = 0;
+    }
+    if (r[0].n_chunks + r[1].n_chunks == 0 || r[0].n_chunks + r[1].n_chunks > SMALL_MAX_CHUNKS) return false;
+    a.range[0] = r[0];
+    a.range[1] = r[1];
+    a.small = true;
+    return true;
+}
+
 static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_out) {
     kg_ctx* ctx = s->ctx;
     if (k == 0 || k > (uint32_t)KG_TOPK_MAX) return fail(ctx, KG_INVALID_ARG, "k=%u outside [1, %d]", k, KG_TOPK_MAX);
@@ -2356,8 +2436,8 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     p->k_last = k;
     p->kk_last = kk;
     if (p->n == 0) return KG_OK;
-    HIP_TRY(ctx, hipMemsetAsync(p->d_pstat, 0, sizeof(uint32_t) * p->n, ctx->stream));
     if (s->n == 0) {
+        HIP_TRY(ctx, hipMemsetAsync(p->d_pstat, 0, sizeof(uint32_t) * p->n, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(d_out, 0, sizeof(uint64_t) * kk * p->n, ctx->stream));
         return KG_OK;
     }
@@ -2367,6 +2447,22 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     const bool dd = dedup_on(p);
     LaunchSelect a = make_select(s, p->dev, dd ? p->d_rorder : p->d_order, dd ? p->n_rep : p->n,
                                  dd ? p->n_rep_fast : p->n_fast, p->n, kk, true, d_out, nullptr, p->d_pstat, &parts);
+    if (select_small(s, a)) {
+        // two launches write every row of d_out and d_pstat: no memset, no side stream, no expansion
+        const size_t slots = (size_t)(a.range[0].n_chunks + a.range[1].n_chunks) * ((a.n_fast + 63) / 64 * 64);
+        kg_status st = ensure_partial(p, 2 * slots);
+        if (st != KG_OK) return st;
+        a.skeys = p->d_partial;
+        a.sub = reinterpret_cast<uint32_t*>(p->d_partial + slots);
+        a.sfhi = a.sub + slots;
+        a.lane_of = dd ? p->d_rlane : p->d_lane;
+        hipEvent_t e0, e1;
+        st = record_begin(ctx, &e0, &e1);
+        if (st != KG_OK) return st;
+        HIP_TRY(ctx, launch_select(a, ctx->stream));
+        return record_end(ctx, e0, e1);
+    }
+    HIP_TRY(ctx, hipMemsetAsync(p->d_pstat, 0, sizeof(uint32_t) * p->n, ctx->stream));
     kg_status st = ensure_partial(p, std::max<size_t>((size_t)parts * p->n * kk, 1));
     if (st != KG_OK) return st;
     a.partial = p->d_partial;

@@ -36,6 +36,7 @@ elif [ "$CFG" = "6" ]; then  # mixed cluster: fast lanes, pruned F_BIG pairs, pr
     python3 tools/pmc_summary.py "$OUT" "$OUT/summary.json" "k_select<" "k_select1<" "k_big_init" "k_big_sel" \
         "k_int_seed" "k_int_filter" "k_int_pairs" "k_merge" || exit $?
 else
-    python3 tools/pmc_summary.py "$OUT" "$OUT/summary.json" "k_select<" "k_select1<" "k_big_init" || exit $?
+    python3 tools/pmc_summary.py "$OUT" "$OUT/summary.json" "k_select<" "k_select1<" "k_big_init" "k_select_small<" \
+        "k_small_finish" || exit $?
 fi
 echo "profile done: $OUT"

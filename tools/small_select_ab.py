@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""A/B aid for the one-pod-block fused top-1 select (k_select_small + k_small_finish; select_small in kg_runtime.cpp)
+under bench.py's warm-up and step counts. It imports the package of the tree it lies in.
+
+Default: config 2's pods (145 distinct rows of 10,000) against config 2's nodes and against synth.mixed()'s nodes,
+which hold many F_BIG records (Restricted nodes, node CPU bind policies: the records the new path evaluates inline
+instead of in k_big_sel), each timed on the new path and with KG_NO_SMALL_SELECT=1 in the same process, alternating;
+the keys of the two paths are compared once per snapshot.
+
+--sweep "c0,c1,copies;...": the new path under KG_SMALL_CHUNKS settings (records per workgroup of storage class 0 / 1,
+lane copies per workgroup: up to 512 threads run the launch-bound variant without scratch), what select_small's
+geometry is set from.
+--nodes also takes config4 (100,000 nodes).
+--lanes N: N all-distinct pods instead of config 2's (the launch then has N lanes, no pod-row reduction).
+--shares "0,0.02,...": synth.mixed()'s nodes thinned to these F_BIG shares (every other node kept, the first F_BIG
+nodes up to the share), for the break-even of the F_BIG gate in select_small. KG_SMALL_ALLOW_BIG=1 (set here) lifts
+that gate so that both paths can be timed above it.
+
+    python tools/small_select_ab.py [--steps 20] [--warmup 3] [--repeat 3] [--nodes config2,mixed] [--sweep ...]
+
+Prints one JSON line per (nodes, setting, repeat)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--nodes", default="config2,mixed")
+    ap.add_argument("--sweep", default=None)
+    ap.add_argument("--lanes", type=int, default=0)
+    ap.add_argument("--shares", default=None)
+    ap.add_argument("--chunks", default=None, help="KG_SMALL_CHUNKS for the new path's side of the A/B")
+    a = ap.parse_args()
+
+    import numpy as np
+
+    from koordinator_amd import abi, engine, synth
+
+    cfg, nodes2, pods = synth.cluster(2)
+    if a.lanes:
+        pods = abi.take(pods, np.arange(a.lanes))
+        pods["req_eph"] = (pods["req_eph"] + np.arange(a.lanes)).astype(np.int64)
+    ctx = engine.Context(0)
+    batch = engine.PodBatch(ctx, pods)
+    lanes = batch.select_lanes()
+
+    def time_select(snap):
+        for _ in range(a.warmup):
+            engine.eval_select_async(snap, batch, 1)
+        ctx.sync()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            engine.eval_select_async(snap, batch, 1)
+        ctx.sync()
+        return (time.perf_counter() - t0) / a.steps * 1e3
+
+    def with_env(name, value, fn):
+        os.environ[name] = value
+        try:
+            return fn()
+        finally:
+            del os.environ[name]
+
+    def big_of(nodes):
+        big = nodes["numa_policy"] == abi.KG_NUMA_RESTRICTED
+        if "cpu_bind_policy" in nodes:
+            big = big | (nodes["cpu_bind_policy"] != 0)
+        return big
+
+    os.environ["KG_SMALL_ALLOW_BIG"] = "1"
+    sets = [(name, nodes2 if name == "config2" else synth.cluster(4)[1] if name == "config4" else synth.mixed()[1])
+            for name in a.nodes.split(",")]
+    if a.shares:
+        mixed = synth.mixed()[1]
+        mbig = big_of(mixed)
+        rest, bigs = np.flatnonzero(~mbig), np.flatnonzero(mbig)
+        sets = []
+        for sh in (float(x) for x in a.shares.split(",")):
+            k = min(len(bigs), int(round(sh * len(rest) / (1.0 - sh))))
+            sets.append((f"mixed_share_{sh}", abi.take(mixed, np.sort(np.concatenate([rest, bigs[:k]])))))
+    for name, nodes in sets:
+        big = big_of(nodes)
+        snap = engine.Snapshot(ctx, cfg.kg_config(), nodes)
+        keys = engine.eval_select(snap, batch, 1)
+        keys0 = with_env("KG_NO_SMALL_SELECT", "1", lambda: engine.eval_select(snap, batch, 1))
+        head = {"nodes": name, "n_nodes": abi.table_len(nodes), "f_big_share": float(big.mean()), "pods": batch.n,
+                "lanes": lanes[0], "fast_lanes": lanes[1], "steps": a.steps, "warmup": a.warmup,
+                "keys_equal": bool(np.array_equal(keys, keys0)), "feasible_rows": int((keys != 0).sum())}
+        for rep in range(a.repeat):
+            if a.sweep:
+                for setting in a.sweep.split(";"):
+                    ms = with_env("KG_SMALL_CHUNKS", setting, lambda: time_select(snap))
+                    print(json.dumps(dict(head, repeat=rep, chunks=setting, select_ms_small=ms)), flush=True)
+            else:
+                small = with_env("KG_SMALL_CHUNKS", a.chunks, lambda: time_select(snap)) if a.chunks else time_select(snap)
+                general = with_env("KG_NO_SMALL_SELECT", "1", lambda: time_select(snap))
+                print(json.dumps(dict(head, repeat=rep, chunks=a.chunks, select_ms_small=small, select_ms_general=general)),
+                      flush=True)
+        snap.close()
+    batch.close()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
