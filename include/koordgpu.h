@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define KG_ABI_VERSION 13
+#define KG_ABI_VERSION 14
 
 /* LoadAware resource vector width: the default vectorizer is {cpu, memory}
  * (pkg/scheduler/plugins/loadaware/helper.go:162-173, sorted by name). */
@@ -609,6 +609,34 @@ kg_status kg_result_keys(kg_pods* pods, uint64_t* out_keys /* n_pods * k */);
  *   KG_ST_QUOTA        the ElasticQuota PreFilter rejected the pod (no node evaluated, keys 0);
  *   0                  the keys are the complete Filter/Score/selectHost result. */
 kg_status kg_result_status(kg_pods* pods, uint32_t* out_status);
+/* FitError diagnosis of unschedulable pods: per requested pod, the number of nodes of this snapshot that fail with
+ * each Filter reason (ABI 14). The framework's FitError.Error() prints "0/N nodes are available: 8 Insufficient cpu,
+ * 3 node(s) cpu usage exceed threshold." from exactly these counts (upstream k8s.io/kubernetes
+ * pkg/scheduler/framework/types.go FitError.Error: the reasons histogram of Diagnosis.NodeToStatus, "%v %v" items
+ * sorted as strings and joined by ", "; koordinator's tables carry the text, e.g.
+ * coscheduling/core/network_topology_workflow_test.go:1255, core_test.go:569).
+ *   rows[t]  a pod index of the uploaded batch; rows may repeat and come in any order; output row t belongs to
+ *            rows[t]. rows == NULL: every pod in batch order (n_rows must equal the batch size).
+ *   out_counts[t * KG_DIAG_SLOTS + b], b in 0..31: nodes whose counted status word has bit b (KG_ST_*) set;
+ *            slot KG_DIAG_DEV_CODE0 + c, c in 1..15: nodes whose DeviceShare code (KG_ST_DEV_CODE) is c (slot 32
+ *            stays 0); slot KG_DIAG_FEASIBLE: nodes whose counted word is 0; slots 49..63 are written as 0.
+ *   flags    0: the counted word is the pair's status word as kg_eval_verify reports it (every failing plugin's
+ *            bits). KG_DIAG_FIRST_PLUGIN: that word masked to its first non-empty group in the framework's order,
+ *            which stops at a node's first failing plugin: the ElasticQuota PreFilter gate (KG_ST_QUOTA), then the
+ *            filter order of config/manager/scheduler-config.yaml:69-74: KG_ST_NRF_MASK, KG_ST_LA_MASK,
+ *            KG_ST_NUMA_MASK | KG_ST_UNSUPPORTED, KG_ST_DEV_MASK | KG_ST_DEV_RSV, KG_ST_RSV_MASK. The DeviceShare
+ *            code slots and KG_DIAG_FEASIBLE follow the counted word.
+ * Synchronous like kg_eval_verify, with its precondition checks; the counts do not depend on index_base.
+ * Counts of node shards add up: a multi-GPU caller sums the shards' rows on the host. A nonzero slot 31
+ * (KG_ST_UNSUPPORTED) means the pod's diagnosis is incomplete: those pairs need the reference plugins on the host.
+ * KG_INVALID_ARG: out_counts == NULL, a row >= the batch size, unknown flag bits, rows == NULL with another n_rows.
+ * n_rows == 0 writes nothing; a snapshot of 0 nodes writes zeros. */
+#define KG_DIAG_SLOTS 64
+#define KG_DIAG_DEV_CODE0 32   /* slot 32 + c: nodes whose DeviceShare code is c (1..15); slot 32 stays 0 */
+#define KG_DIAG_FEASIBLE 48    /* nodes whose status word is 0 */
+#define KG_DIAG_FIRST_PLUGIN 0x1u
+kg_status kg_eval_diagnose(kg_snap* snap, kg_pods* pods, const uint32_t* rows, uint32_t n_rows, uint32_t flags,
+                           uint32_t* out_counts /* n_rows * KG_DIAG_SLOTS */);
 /* Sequential scheduling of pods[0..n) one at a time with Assume applied on the device between pods
  * (the reference's one-pod-per-cycle semantics). out_node[i] = global node index or -1 (no feasible node,
  * or the selected node's Reserve failed: KG_ST_NUMA_INSUF_* in out_reason).

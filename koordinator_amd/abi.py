@@ -11,7 +11,7 @@ from typing import Dict
 
 import numpy as np
 
-KG_ABI_VERSION = 13
+KG_ABI_VERSION = 14
 KG_LA_R = 2
 KG_NSCALAR = 2
 KG_MAX_ZONES = 4
@@ -131,6 +131,12 @@ KG_ST_RSV_MASK = 0x1C000000
 KG_ST_QUOTA = 0x20000000
 KG_ST_DEV_RSV = 0x40000000  # "Reservation(s) Insufficient gpu devices"
 KG_ST_UNSUPPORTED = 0x80000000
+# kg_eval_diagnose: counters per requested pod (slot b < 32: nodes with status bit b; KG_DIAG_DEV_CODE0 + c: nodes whose
+# DeviceShare code is c; KG_DIAG_FEASIBLE: nodes with a zero counted word) and its flag
+KG_DIAG_SLOTS = 64
+KG_DIAG_DEV_CODE0 = 32
+KG_DIAG_FEASIBLE = 48
+KG_DIAG_FIRST_PLUGIN = 0x1
 # kg_batch_schedule per-pod result codes
 KG_BATCH_ASSUMED, KG_BATCH_FAILED, KG_BATCH_SIBLING, KG_BATCH_ROLLED_BACK, KG_BATCH_NO_PLAN = range(5)
 

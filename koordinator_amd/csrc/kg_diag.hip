@@ -1,0 +1,151 @@
+// kg_diag.hip — CDNA4 (gfx950) kernel of the FitError diagnosis (kg_eval_diagnose): per requested pod, how many
+// nodes fail with each Filter reason.
+//
+//   k_diagnose  lane = requested row (a pod of the batch), the wave walks a chunk of node records in uniform order
+//               (blockIdx.y = chunk), as k_select's integer path does. Each pair gives two 32-bit words: the counted
+//               status word (the pair's KG_ST_* bits, or their first non-empty plugin group) and a derived word
+//               (one-hot DeviceShare code, feasible bit). Bit b of a word is counted in byte b / 8 of accumulator
+//               b % 8: acc[s] += (w >> s) & 0x01010101, eight adds per word instead of one test-and-add per bit.
+//               A byte holds at most 255, so a lane walks at most DIAG_MAX_CHUNK records per launch; the chunk's
+//               nonzero counters are then added into the row's KG_DIAG_SLOTS counters by atomicAdd (integer adds:
+//               exact in any order).
+// The plain plugin set evaluates a pair with eval_pair (filters only: no score, no zone), the config-5 set with
+// eval_pair_ext behind the ElasticQuota gate, as the verify kernels do: the status words are theirs bit for bit.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+
+#include "kg_cpuset_reserve.h"
+#include "kg_diag.h"
+#include "kg_ext.h"
+#include "kg_ext_wave.h"
+#include "kg_kernels.h"
+
+namespace kg {
+
+// The framework stops at a node's first failing plugin: the PreFilter gate, then the filter order of
+// config/manager/scheduler-config.yaml:69-74. A word with bits of no group (none is defined) stays whole.
+__device__ __forceinline__ uint32_t diag_first_plugin(uint32_t w) {
+    constexpr uint32_t G[6] = {KG_ST_QUOTA,
+                               KG_ST_NRF_MASK,
+                               KG_ST_LA_MASK,
+                               KG_ST_NUMA_MASK | KG_ST_UNSUPPORTED,
+                               KG_ST_DEV_MASK | KG_ST_DEV_RSV,
+                               KG_ST_RSV_MASK};
+    uint32_t m = w;
+#pragma unroll
+    for (int g = 5; g >= 0; g--) m = (w & G[g]) ? G[g] : m;
+    return w & m;
+}
+
+// Derived word of a counted word: bit c = its DeviceShare code is c (1..15), bit 16 = it is 0 (feasible); bit k is
+// slot KG_DIAG_DEV_CODE0 + k.
+static_assert(KG_DIAG_FEASIBLE - KG_DIAG_DEV_CODE0 == 16 && KG_DIAG_SLOTS == 64, "slot layout of the derived word");
+__device__ __forceinline__ uint32_t diag_derived(uint32_t w) {
+    const uint32_t code = KG_ST_DEV_CODE(w);
+    return (code ? 1u << code : 0u) | (w == 0u ? 1u << 16 : 0u);
+}
+
+// Packed counters: byte f of acc[s] counts bit 8 f + s. One add per pair and byte: the launcher keeps a lane's pairs
+// per launch at or below DIAG_MAX_CHUNK, so no byte carries into its neighbour.
+static_assert(DIAG_MAX_CHUNK <= 255, "a packed 8-bit counter takes one add per record of the chunk");
+struct DiagAcc {
+    uint32_t w[8], d[8];
+};
+__device__ __forceinline__ void diag_count(DiagAcc& a, uint32_t w, uint32_t d) {
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        a.w[s] += (w >> s) & 0x01010101u;
+        a.d[s] += (d >> s) & 0x01010101u;
+    }
+}
+
+// dst[0..64) += the lane's counters (the nonzero ones: a pod fails with a few reasons)
+__device__ __forceinline__ void diag_flush(const DiagAcc& a, uint32_t* __restrict__ dst) {
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+#pragma unroll
+        for (int f = 0; f < 4; f++) {
+            const uint32_t cw = (a.w[s] >> (8 * f)) & 0xFFu, cd = (a.d[s] >> (8 * f)) & 0xFFu;
+            if (cw) atomicAdd(dst + 8 * f + s, cw);
+            if (8 * f + s <= KG_DIAG_FEASIBLE - KG_DIAG_DEV_CODE0 && cd) atomicAdd(dst + KG_DIAG_DEV_CODE0 + 8 * f + s, cd);
+        }
+    }
+}
+
+// Records [begin + chunk * y, ...) of [begin, end) for the rows of block x; counts[t][KG_DIAG_SLOTS] zeroed by the
+// launcher. chunk <= DIAG_MAX_CHUNK.
+template <bool EXACT, bool EXT>
+__global__ __launch_bounds__(256) void k_diagnose(const NodeRec* __restrict__ nodes, const ZoneRec* __restrict__ zones,
+                                                  ExtDev e, PodsDev pods, const uint32_t* __restrict__ rows,
+                                                  uint32_t n_rows, uint32_t begin, uint32_t end, uint32_t chunk, KCfg cfg,
+                                                  const uint32_t* __restrict__ qst, uint32_t first_plugin,
+                                                  uint32_t* __restrict__ counts) {
+    const GridBlock b = xcd_block();  // whole record chunks per XCD (kg_eval.h)
+    const uint32_t t = b.x * blockDim.x + threadIdx.x;
+    if ((t & ~63u) >= n_rows) return;  // uniform: a wave past the last row (no barrier below)
+    const bool live = t < n_rows;
+    const uint32_t j = live ? (rows ? rows[t] : t) : 0u;
+    const PodV p = load_pod(pods, j);
+    const uint32_t lo = begin + b.y * chunk;
+    const uint32_t hi = min(end, lo + chunk);
+    DiagAcc a;
+#pragma unroll
+    for (int s = 0; s < 8; s++) a.w[s] = a.d[s] = 0u;
+    if constexpr (EXT) {
+        const PodX px = load_podx(pods, j);
+        const uint32_t q = live ? qst[j] : 1u;  // idle lanes: decided, no pair evaluated
+        for (uint32_t rec = lo; rec < hi; rec++) {
+            uint32_t w = eval_pair_ext<EXACT>(cfg, e, nodes[rec].v, zones + rec, dev_of(e, rec), rec, p, px, q).status;
+            if (first_plugin) w = diag_first_plugin(w);
+            diag_count(a, w, diag_derived(w));
+        }
+    } else {
+        for (uint32_t rec = lo; rec < hi; rec++) {
+            uint32_t w = eval_pair<EXACT, false, true, false, false>(cfg, nodes[rec].v, zones + rec, p).status;
+            if (first_plugin) w = diag_first_plugin(w);
+            diag_count(a, w, diag_derived(w));
+        }
+    }
+    if (live) diag_flush(a, counts + (size_t)t * KG_DIAG_SLOTS);
+}
+
+// KG_DIAG_BLOCKS: workgroup target of the launch (tuning aid; 1 gives every lane chunks of DIAG_MAX_CHUNK records).
+// Read per call: tests switch it per case.
+static uint32_t diag_target_blocks() {
+    const char* e = std::getenv("KG_DIAG_BLOCKS");
+    const long x = e ? std::strtol(e, nullptr, 10) : 0;
+    return (x >= 1 && x <= 65536) ? (uint32_t)x : DIAG_TARGET_BLOCKS;
+}
+
+hipError_t launch_diagnose(const NodeRec* nodes, const ZoneRec* zones, const ExtDev& e, bool ext, const PodsDev& pods,
+                           const uint32_t* rows, uint32_t n_rows, uint32_t n_nodes, const KCfg& cfg, bool exact,
+                           const uint32_t* qst, bool first_plugin, uint32_t* counts, hipStream_t s) {
+    if (n_rows == 0 || n_nodes == 0) return hipSuccess;
+    // whole waves of rows, up to four per workgroup: a short row list leaves no idle wave walking records
+    const uint32_t block = std::min<uint32_t>(256u, (n_rows + 63u) / 64u * 64u);
+    const uint32_t chunk = diag_chunk(n_nodes, n_rows, block, diag_target_blocks());
+    const uint32_t gx = (n_rows + block - 1) / block;
+    constexpr uint32_t MAX_Y = 65535;  // gridDim.y; larger snapshots take several launches
+    for (uint64_t begin = 0; begin < n_nodes; begin += (uint64_t)MAX_Y * chunk) {
+        const uint32_t end = (uint32_t)std::min<uint64_t>(n_nodes, begin + (uint64_t)MAX_Y * chunk);
+        const dim3 grid(gx, (end - (uint32_t)begin + chunk - 1) / chunk);
+#define KG_DIAG_LAUNCH(EXACT, EXT)                                                                                     \
+    k_diagnose<EXACT, EXT><<<grid, block, 0, s>>>(nodes, zones, e, pods, rows, n_rows, (uint32_t)begin, end, chunk, cfg, \
+                                                  qst, first_plugin ? 1u : 0u, counts)
+        if (ext) {
+            if (exact) KG_DIAG_LAUNCH(true, true);
+            else KG_DIAG_LAUNCH(false, true);
+        } else {
+            if (exact) KG_DIAG_LAUNCH(true, false);
+            else KG_DIAG_LAUNCH(false, false);
+        }
+#undef KG_DIAG_LAUNCH
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
+}  // namespace kg

@@ -28,6 +28,7 @@
 
 #include "../../include/koordgpu.h"
 #include "kg_dedup.h"
+#include "kg_diag.h"
 #include "kg_kernels.h"
 #include "kg_layout.h"
 
@@ -235,6 +236,10 @@ struct kg_pods {
     uint64_t* h_keys = nullptr;    // pinned download staging of the keys [cap][KG_TOPK_MAX]
     uint32_t* d_pstat = nullptr;   // per pod: KG_ST_UNSUPPORTED / KG_ST_QUOTA of the last select (kg_result_status)
     uint32_t* d_reason = nullptr;  // replay: per pod OR of the filter status bits (kg_replay out_reason)
+    // kg_eval_diagnose: the requested rows and their KG_DIAG_SLOTS counters, grown on demand (ensure_diag)
+    uint32_t* d_diag_rows = nullptr;
+    uint32_t* d_diag = nullptr;
+    size_t diag_cap = 0;  // rows
     DevSum* d_devsum = nullptr;    // per record DevSum of the last config-5 select
     size_t devsum_cap = 0;
     uint64_t* d_gz = nullptr;      // gpu_zone_sum per (class-1 record, GPU request class) of the last config-5 select
@@ -1671,7 +1676,8 @@ kg_status kg_pods_destroy(kg_pods* p) {
     for (void* b : {(void*)p->d_in, (void*)p->d_keys, (void*)p->d_winners, (void*)p->d_step, (void*)p->d_partial,
                     (void*)p->d_gather, (void*)p->d_qst, (void*)p->d_dev_max, (void*)p->d_rsv_max, (void*)p->d_pref,
                     (void*)p->d_minors, (void*)p->d_buckets, (void*)p->d_aout, (void*)p->d_tkeys, (void*)p->d_pstat,
-                    (void*)p->d_reason, (void*)p->d_devsum, (void*)p->d_gz, (void*)p->d_spec, (void*)p->d_split, (void*)p->d_batch, (void*)p->d_rcode, (void*)p->d_done, (void*)p->d_rec, (void*)p->d_xpairs})
+                    (void*)p->d_reason, (void*)p->d_devsum, (void*)p->d_gz, (void*)p->d_spec, (void*)p->d_split, (void*)p->d_batch, (void*)p->d_rcode, (void*)p->d_done, (void*)p->d_rec, (void*)p->d_xpairs,
+                    (void*)p->d_diag_rows, (void*)p->d_diag})
         hipFree(b);
     hipHostFree(p->h_in);
     hipHostFree(p->h_keys);
@@ -1780,6 +1786,66 @@ kg_status kg_eval_verify(kg_snap* s, kg_pods* p, kg_verify_out* out) {
     if (e == hipSuccess && out->score_rsv) std::memset(out->score_rsv, 0, 8 * pairs);
     hipFree(buf);
     HIP_TRY(ctx, e);
+    return KG_OK;
+}
+
+// Scratch of kg_eval_diagnose for n_rows requested rows: no allocation on the steady path.
+static kg_status ensure_diag(kg_pods* p, size_t n_rows) {
+    kg_ctx* ctx = p->ctx;
+    if (n_rows <= p->diag_cap) return KG_OK;
+    if (p->d_diag || p->d_diag_rows) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        hipFree(p->d_diag);
+        hipFree(p->d_diag_rows);
+        p->d_diag = p->d_diag_rows = nullptr;
+        p->diag_cap = 0;
+    }
+    const size_t cap = std::max<size_t>(n_rows, 64);
+    HIP_TRY(ctx, hipMalloc(&p->d_diag, sizeof(uint32_t) * KG_DIAG_SLOTS * cap));
+    HIP_TRY(ctx, hipMalloc(&p->d_diag_rows, sizeof(uint32_t) * cap));
+    p->diag_cap = cap;
+    return KG_OK;
+}
+
+kg_status kg_eval_diagnose(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_t n_rows, uint32_t flags,
+                           uint32_t* out_counts) {
+    kg_status st = check_pair(s, p);
+    if (st != KG_OK) return st;
+    kg_ctx* ctx = s->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (flags & ~KG_DIAG_FIRST_PLUGIN) return fail(ctx, KG_INVALID_ARG, "diagnose flags 0x%x", flags);
+    if (!rows && n_rows != p->n)
+        return fail(ctx, KG_INVALID_ARG, "rows == NULL with n_rows %u != batch size %u", n_rows, p->n);
+    if (rows)
+        for (uint32_t t = 0; t < n_rows; t++)
+            if (rows[t] >= p->n) return fail(ctx, KG_INVALID_ARG, "rows[%u] = %u >= batch size %u", t, rows[t], p->n);
+    if (!out_counts) return fail(ctx, KG_INVALID_ARG, "null counts output");
+    st = check_views(s);
+    if (st != KG_OK) return st;
+    if (s->ext()) {
+        st = check_ext(s);
+        if (st != KG_OK) return st;
+    }
+    if (n_rows == 0) return KG_OK;
+    const size_t words = (size_t)n_rows * KG_DIAG_SLOTS;
+    if (s->n == 0) {
+        std::memset(out_counts, 0, sizeof(uint32_t) * words);
+        return KG_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = ensure_diag(p, n_rows);
+    if (st != KG_OK) return st;
+    HIP_TRY(ctx, hipMemsetAsync(p->d_diag, 0, sizeof(uint32_t) * words, ctx->stream));
+    if (rows)
+        HIP_TRY(ctx, hipMemcpyAsync(p->d_diag_rows, rows, sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice, ctx->stream));
+    const ExtDev e = s->ext_dev();
+    if (s->ext())  // the ElasticQuota PreFilter of every pod of the batch, as kg_eval_verify runs it
+        HIP_TRY(ctx, launch_ext_gate(p->dev, p->n, e, s->cfg.plugins, p->d_qst, nullptr, ctx->stream));
+    HIP_TRY(ctx, launch_diagnose(s->d_nodes, s->d_zones, e, s->ext(), p->dev, rows ? p->d_diag_rows : nullptr, n_rows, s->n,
+                                 s->kcfg, force_exact(), p->d_qst, (flags & KG_DIAG_FIRST_PLUGIN) != 0, p->d_diag,
+                                 ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_counts, p->d_diag, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return KG_OK;
 }
 

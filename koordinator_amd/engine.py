@@ -79,6 +79,8 @@ def lib():
     L.kg_pods_destroy.restype = st
     L.kg_eval_verify.argtypes = [vp, vp, P(abi.KgVerifyOut)]
     L.kg_eval_verify.restype = st
+    L.kg_eval_diagnose.argtypes = [vp, vp, P(u32), u32, u32, P(u32)]
+    L.kg_eval_diagnose.restype = st
     L.kg_eval_select.argtypes = [vp, vp, u32]
     L.kg_eval_select.restype = st
     L.kg_result_keys.argtypes = [vp, P(u64)]
@@ -380,6 +382,24 @@ def eval_verify(snap: Snapshot, pods: PodBatch) -> abi.VerifyResult:
     s = res.struct()
     snap.ctx.check(snap.ctx.L.kg_eval_verify(snap.h, pods.h, C.byref(s)), "kg_eval_verify")
     return res
+
+
+def eval_diagnose(snap: Snapshot, pods: PodBatch, rows=None, first_plugin: bool = True) -> np.ndarray:
+    """kg_eval_diagnose: reason node counts [n_rows, KG_DIAG_SLOTS] (uint32) of the pods `rows` (batch indices, any
+    order, repeats allowed; None = every pod). first_plugin: count each node under its first failing plugin only, as
+    the framework's Diagnosis does (reasons.fit_error reads such rows); False: every failing plugin's bits."""
+    P = C.POINTER(C.c_uint32)
+    flags = abi.KG_DIAG_FIRST_PLUGIN if first_plugin else 0
+    if rows is None:
+        n_rows, rp = pods.n, None
+    else:
+        rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        n_rows = len(rows)
+        rp = (rows if n_rows else np.zeros(1, np.uint32)).ctypes.data_as(P)  # an empty list is not "every pod"
+    out = np.zeros((max(n_rows, 1), abi.KG_DIAG_SLOTS), np.uint32)
+    snap.ctx.check(snap.ctx.L.kg_eval_diagnose(snap.h, pods.h, rp, n_rows, flags, out.ctypes.data_as(P)),
+                   "kg_eval_diagnose")
+    return out[:n_rows]
 
 
 def eval_select_async(snap: Snapshot, pods: PodBatch, k: int = 1):

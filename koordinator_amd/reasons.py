@@ -23,6 +23,49 @@ from . import abi
 DEFAULT_SCALARS = ("kubernetes.io/batch-cpu", "kubernetes.io/batch-memory")
 
 
+def _nrf_table(scalar_names):
+    return (
+        (abi.KG_ST_NRF_PODS, "Too many pods"),
+        (abi.KG_ST_NRF_CPU, "Insufficient cpu"),
+        (abi.KG_ST_NRF_MEM, "Insufficient memory"),
+        (abi.KG_ST_NRF_EPH, "Insufficient ephemeral-storage"),
+        (abi.KG_ST_NRF_SC0, f"Insufficient {scalar_names[0]}"),
+        (abi.KG_ST_NRF_SC1, f"Insufficient {scalar_names[1]}"),
+    )
+
+
+LA_EXPIRED_REASON = "node(s) nodeMetric expired"
+LA_RESOURCES = ((abi.KG_ST_LA_CPU, "cpu"), (abi.KG_ST_LA_MEM, "memory"))
+
+
+def _la_usage_reason(res: str, aggregated: bool) -> str:
+    return f"node(s) {res} aggregated usage exceed threshold" if aggregated else f"node(s) {res} usage exceed threshold"
+
+
+NUMA_TABLE = (
+    (abi.KG_ST_NUMA_AMP_CPU, "Insufficient amplified cpu"),
+    (abi.KG_ST_NUMA_CONFLICT, "node(s) NUMA Topology policy not match"),
+    (abi.KG_ST_NUMA_NO_RES, "node(s) missing NUMA resources"),
+    (abi.KG_ST_NUMA_ALIGN, "Unaligned NUMA Hint cause <hints>"),
+    (abi.KG_ST_NUMA_UNSATISFIED, "Unsatisfied NUMA <resource>"),
+    (abi.KG_ST_NUMA_CPU_TOPO, "node(s) invalid CPU Topology"),
+    (abi.KG_ST_NUMA_CPU_BIND, "node(s) cpu bind policy conflicts / SMT alignment / invalid requested cpus"),
+    (abi.KG_ST_NUMA_CPUS, "not enough cpus available to satisfy request"),
+    # Reserve of a BestEffort node (plugin.go:612-623, resource_manager.go:135,300-309)
+    (abi.KG_ST_NUMA_INSUF_CPU, "Insufficient NUMA cpu"),
+    (abi.KG_ST_NUMA_INSUF_MEM, "Insufficient NUMA memory"),
+    (abi.KG_ST_NUMA_INSUF_NODE, "node(s) Insufficient NUMA Node resources"),
+)
+DEV_RSV_REASON = "Reservation(s) Insufficient gpu devices"  # makeReasonsByReservation (deviceshare/plugin.go)
+RSV_TABLE = (
+    (abi.KG_ST_RSV_AFFINITY, "node(s) no reservations match reservation affinity"),
+    (abi.KG_ST_RSV_NODE, "Insufficient <resource> by node"),
+    (abi.KG_ST_RSV_RESERVATION, "node(s) no reservation(s) to meet the requirements"),
+)
+QUOTA_REASON = "Insufficient quotas, <quota state>"
+HOST_PATH_REASON = "pair evaluated by the reference plugin on the host"
+
+
 def plugin_reasons(bits: int, scalar_names=DEFAULT_SCALARS) -> dict:
     """{plugin name: [reason, ...]} of one status word (or an OR of several)."""
     bits = int(bits)
@@ -31,57 +74,29 @@ def plugin_reasons(bits: int, scalar_names=DEFAULT_SCALARS) -> dict:
     def add(plugin, msg):
         out.setdefault(plugin, []).append(msg)
 
-    nrf = (
-        (abi.KG_ST_NRF_PODS, "Too many pods"),
-        (abi.KG_ST_NRF_CPU, "Insufficient cpu"),
-        (abi.KG_ST_NRF_MEM, "Insufficient memory"),
-        (abi.KG_ST_NRF_EPH, "Insufficient ephemeral-storage"),
-        (abi.KG_ST_NRF_SC0, f"Insufficient {scalar_names[0]}"),
-        (abi.KG_ST_NRF_SC1, f"Insufficient {scalar_names[1]}"),
-    )
-    for bit, msg in nrf:
+    for bit, msg in _nrf_table(scalar_names):
         if bits & bit:
             add("NodeResourcesFit", msg)
     if bits & abi.KG_ST_LA_EXPIRED:
-        add("LoadAwareScheduling", "node(s) nodeMetric expired")
-    for bit, res in ((abi.KG_ST_LA_CPU, "cpu"), (abi.KG_ST_LA_MEM, "memory")):
+        add("LoadAwareScheduling", LA_EXPIRED_REASON)
+    for bit, res in LA_RESOURCES:
         if bits & bit:
-            if bits & abi.KG_ST_LA_AGG:
-                add("LoadAwareScheduling", f"node(s) {res} aggregated usage exceed threshold")
-            else:
-                add("LoadAwareScheduling", f"node(s) {res} usage exceed threshold")
-    numa = (
-        (abi.KG_ST_NUMA_AMP_CPU, "Insufficient amplified cpu"),
-        (abi.KG_ST_NUMA_CONFLICT, "node(s) NUMA Topology policy not match"),
-        (abi.KG_ST_NUMA_NO_RES, "node(s) missing NUMA resources"),
-        (abi.KG_ST_NUMA_ALIGN, "Unaligned NUMA Hint cause <hints>"),
-        (abi.KG_ST_NUMA_UNSATISFIED, "Unsatisfied NUMA <resource>"),
-        (abi.KG_ST_NUMA_CPU_TOPO, "node(s) invalid CPU Topology"),
-        (abi.KG_ST_NUMA_CPU_BIND, "node(s) cpu bind policy conflicts / SMT alignment / invalid requested cpus"),
-        (abi.KG_ST_NUMA_CPUS, "not enough cpus available to satisfy request"),
-        # Reserve of a BestEffort node (plugin.go:612-623, resource_manager.go:135,300-309)
-        (abi.KG_ST_NUMA_INSUF_CPU, "Insufficient NUMA cpu"),
-        (abi.KG_ST_NUMA_INSUF_MEM, "Insufficient NUMA memory"),
-        (abi.KG_ST_NUMA_INSUF_NODE, "node(s) Insufficient NUMA Node resources"),
-    )
-    for bit, msg in numa:
+            add("LoadAwareScheduling", _la_usage_reason(res, bool(bits & abi.KG_ST_LA_AGG)))
+    for bit, msg in NUMA_TABLE:
         if bits & bit:
             add("NodeNUMAResource", msg)
     code = abi.dev_code(bits)
     if code:  # GPU allocator reasons (deviceshare/allocator_gpu.go:31-41, device_allocator.go:432)
         add("DeviceShare", DEV_CODE_REASONS.get(code, "Insufficient gpu devices"))
-    if bits & abi.KG_ST_DEV_RSV:  # makeReasonsByReservation (deviceshare/plugin.go)
-        add("DeviceShare", "Reservation(s) Insufficient gpu devices")
-    if bits & abi.KG_ST_RSV_AFFINITY:
-        add("Reservation", "node(s) no reservations match reservation affinity")
-    if bits & abi.KG_ST_RSV_NODE:
-        add("Reservation", "Insufficient <resource> by node")
-    if bits & abi.KG_ST_RSV_RESERVATION:
-        add("Reservation", "node(s) no reservation(s) to meet the requirements")
+    if bits & abi.KG_ST_DEV_RSV:
+        add("DeviceShare", DEV_RSV_REASON)
+    for bit, msg in RSV_TABLE:
+        if bits & bit:
+            add("Reservation", msg)
     if bits & abi.KG_ST_QUOTA:
-        add("ElasticQuota", "Insufficient quotas, <quota state>")
+        add("ElasticQuota", QUOTA_REASON)
     if bits & abi.KG_ST_UNSUPPORTED:
-        add("(host path)", "pair evaluated by the reference plugin on the host")
+        add("(host path)", HOST_PATH_REASON)
     return out
 
 
@@ -103,6 +118,65 @@ DEV_CODE_REASONS = {
 def reasons(bits: int, scalar_names=DEFAULT_SCALARS) -> list:
     """Flat list of the reasons in plugin filter order."""
     return [m for msgs in plugin_reasons(bits, scalar_names).values() for m in msgs]
+
+
+def _slot(bit: int) -> int:
+    return int(bit).bit_length() - 1
+
+
+def reason_counts(counts_row, scalar_names=DEFAULT_SCALARS) -> dict:
+    """{reason string: number of nodes} of one row of engine.eval_diagnose (kg_eval_diagnose): the histogram the
+    framework's FitError prints. The strings are plugin_reasons'; DeviceShare's come from the code slots
+    (KG_DIAG_DEV_CODE0 + code), not from the code's raw bits; bits that map to one string add up; zero counts are
+    left out.
+
+    LoadAware's "aggregated" wording is one bit beside the cpu / memory bit of the same node, so the counts tell how
+    many nodes carry it but not, when both resources fail somewhere and only some of those nodes aggregate, how they
+    split: then the cpu nodes are taken to be the aggregated ones first (exact whenever every failing node, or none, or
+    one resource only is involved)."""
+    c = [int(v) for v in counts_row]
+    if len(c) != abi.KG_DIAG_SLOTS:
+        raise ValueError(f"a diagnosis row has {abi.KG_DIAG_SLOTS} counters, got {len(c)}")
+    out: dict = {}
+
+    def add(msg, n):
+        if n:
+            out[msg] = out.get(msg, 0) + n
+
+    for bit, msg in _nrf_table(scalar_names):
+        add(msg, c[_slot(bit)])
+    add(LA_EXPIRED_REASON, c[_slot(abi.KG_ST_LA_EXPIRED)])
+    agg = c[_slot(abi.KG_ST_LA_AGG)]
+    for bit, res in LA_RESOURCES:
+        n = c[_slot(bit)]
+        a = min(n, agg)
+        agg -= a
+        add(_la_usage_reason(res, True), a)
+        add(_la_usage_reason(res, False), n - a)
+    for bit, msg in NUMA_TABLE:
+        add(msg, c[_slot(bit)])
+    for code in range(1, 16):
+        add(DEV_CODE_REASONS.get(code, "Insufficient gpu devices"), c[abi.KG_DIAG_DEV_CODE0 + code])
+    add(DEV_RSV_REASON, c[_slot(abi.KG_ST_DEV_RSV)])
+    for bit, msg in RSV_TABLE:
+        add(msg, c[_slot(bit)])
+    add(QUOTA_REASON, c[_slot(abi.KG_ST_QUOTA)])
+    add(HOST_PATH_REASON, c[_slot(abi.KG_ST_UNSUPPORTED)])
+    return out
+
+
+def fit_error(counts_row, n_nodes: int, scalar_names=DEFAULT_SCALARS, prefilter_msg=None) -> str:
+    """The text of upstream's FitError.Error() (k8s.io/kubernetes pkg/scheduler/framework/types.go) for one row of
+    first-plugin counts (engine.eval_diagnose(first_plugin=True): the framework records one failing plugin per node):
+    "0/<n_nodes> nodes are available: " + the "<count> <reason>" items sorted as strings, joined by ", " + ".";
+    with no failing node just "0/<n_nodes> nodes are available:" (coscheduling/core/core_test.go:569). A pod the
+    ElasticQuota PreFilter rejected carries the PreFilter message alone (prefilter_msg: the plugin's formatted text,
+    default the placeholder of plugin_reasons). n_nodes: all nodes of the cluster (the sum over shards)."""
+    head = f"0/{int(n_nodes)} nodes are available:"
+    if int(counts_row[_slot(abi.KG_ST_QUOTA)]):
+        return f"{head} {prefilter_msg or QUOTA_REASON}."
+    items = sorted(f"{n} {msg}" for msg, n in reason_counts(counts_row, scalar_names).items())
+    return f"{head} {', '.join(items)}." if items else head
 
 
 def loadaware_status(bits: int):

@@ -65,7 +65,7 @@ open(out, "w").write(src)
 flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-Wno-unused-value",
          "-I" + os.path.join(R, "koordinator_amd/csrc")]
 objs = [os.path.join(R, "build", f) for f in ("kg_kernels.hip.o", "kg_ext.hip.o", "kg_ext_batch.hip.o", "kg_cpuset.hip.o",
-                                              "kg_runtime.cpp.o")]
+                                              "kg_diag.hip.o", "kg_runtime.cpp.o")]
 subprocess.check_call(["/opt/rocm/bin/hipcc", *flags, "-c", out, "-o", out + ".o"])
 subprocess.check_call(["/opt/rocm/bin/hipcc", *flags, "-shared", out + ".o", *objs, "-o",
                        os.path.join(R, "tools/timing/libkoordgpu_t%s.so" % ("_stub" if "--stub" in sys.argv else "_split" if "--split" in sys.argv else "")), "-L/opt/rocm/lib", "-lrccl",
