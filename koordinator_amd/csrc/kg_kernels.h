@@ -56,14 +56,18 @@ struct LaunchSelect {
     // the launch stream before the fast kernels, joined back after them
     hipStream_t side;
     hipEvent_t fork, join;
-    // one-pod-block fused top-1 select (k_select_small + k_small_finish): K == 1, fused, every lane a fast lane, at
-    // most 256 of them. Two launches, no memset of out / pstat, no atomics, no side stream; range[c] holds this path's
-    // chunks (at most SMALL_MAX_CHUNK records each, SMALL_MAX_CHUNKS in all), the F_BIG records are taken inline
+    // one-pod-block fused top-1 select (k_select_small, k_small_finish): K == 1, fused, every lane a fast lane, at
+    // most 256 of them. No memset of out / pstat, no side stream; range[c] holds this path's chunks (at most
+    // SMALL_MAX_CHUNK records each, SMALL_MAX_CHUNKS in all), the F_BIG records are taken inline. small_replicas > 0:
+    // one launch, the workgroups fold into that many replicas of per-lane accumulators and the last to arrive writes
+    // every row; 0: two launches, per-chunk slots merged by k_small_finish
     bool small;
-    uint64_t* skeys;         // [chunks][lanes rounded up to whole waves] best key per chunk and lane
+    uint64_t* skeys;         // [chunks or replicas][lanes rounded up to whole waves] best key per chunk and lane
     uint32_t *sub, *sfhi;    // same shape: highest bound of a KG_ST_UNSUPPORTED pair, high word of the best fast key
     const uint8_t* lane_of;  // per row of [0, n_rows) the lane whose result it takes
     uint32_t small_slices;   // waves sets per workgroup, each walking its part of the workgroup's chunk
+    uint32_t small_replicas;  // replicas of the accumulators; they and *sticket are zero before and after every launch
+    uint32_t* sticket;        // arrival counter of the launch
 };
 constexpr uint32_t SMALL_MAX_CHUNK = 64, SMALL_MAX_CHUNKS = 4096;
 constexpr uint32_t SMALL_WG = 1024;  // most threads of a k_select_small workgroup

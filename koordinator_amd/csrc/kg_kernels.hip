@@ -5,8 +5,9 @@
 //              top-K per lane; per-(chunk, pod) partial keys. Specialised per node storage class
 //              (records are stored grouped by class) and per enabled-plugin set.
 //   k_select_small / k_small_finish  the fused top-1 select of at most 256 fast lanes: both storage classes and
-//              the F_BIG records in one launch, per-chunk slots instead of atomics, then one merge-and-expand launch
-//              that writes every row (no memset, no k_big_sel, no k_expand_keys).
+//              the F_BIG records in one launch that also finishes: the workgroups fold into a few replicas of per-lane
+//              accumulators by atomic maxima and the last to arrive writes every row (no memset, no k_big_sel, no
+//              k_expand_keys). For many rows, or on request: per-chunk slots and k_small_finish as a second launch.
 //   k_big_sel  the nodes outside the float64 fast path (F_BIG records) for the fast lanes, on the
 //              integer path, chunked over the device's F_BIG list.
 //   k_merge    per pod: top-K over partial keys (global selectHost of one shard or of the
@@ -308,7 +309,9 @@ __global__ __launch_bounds__(256) KG_SEL1_ATTR void k_select1(const NodeRec* __r
 }
 
 // One-pod-block fused top-1 select (LaunchSelect.small): both storage classes and the F_BIG records in one launch,
-// no atomics and nothing to zero. grid (1, nc1 + nc0): workgroups [0, nc1) take class-1 chunks of chunk1 records (the
+// and nothing to zero in a steady-state step. acc_r > 0: the launch finishes itself (the epilogue below: replicated
+// accumulators, a ticket, the last workgroup writes out / pstat of every row); acc_r == 0: the slot form
+// described here, no atomics, k_small_finish follows. grid (1, nc1 + nc0): workgroups [0, nc1) take class-1 chunks of chunk1 records (the
 // zone walk makes them the dearer ones: they start first), the others class-0 chunks of chunk0; at most 64 records
 // per chunk. A block is `slices` copies of the fast lanes rounded up to whole waves (lp): slice s walks the s-th part
 // of the chunk, so a compute unit holds several waves per SIMD that hide each other's record loads (one wave per SIMD
@@ -329,7 +332,10 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
                                                            uint32_t n_end, uint32_t chunk0, uint32_t chunk1, uint32_t nc1,
                                                            uint32_t index_base, KCfg cfg, uint64_t* __restrict__ skeys,
                                                            uint32_t* __restrict__ sub, uint32_t* __restrict__ sfhi,
-                                                           const uint32_t* __restrict__ order) {
+                                                           const uint32_t* __restrict__ order, uint32_t acc_r,
+                                                           uint32_t* __restrict__ ticket,
+                                                           const uint8_t* __restrict__ lane_of, uint32_t n_rows,
+                                                           uint64_t* __restrict__ out, uint32_t* __restrict__ pstat) {
     __shared__ uint64_t lk[WG];
     __shared__ uint2 ls[WG];
     const uint32_t c = xcd_block().y, slices = blockDim.x / lp;
@@ -399,7 +405,68 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
         lk[threadIdx.x] = top;
         ls[threadIdx.x] = st;
         __syncthreads();
+        if (sl == 0) {
+            for (uint32_t s2 = 1; s2 < slices; s2++) {
+                const uint64_t k2 = lk[s2 * lp + j];
+                const uint2 t2 = ls[s2 * lp + j];
+                st.x = max(st.x, t2.x);
+                st.y = max(st.y, t2.y);
+                top = k2 > top ? k2 : top;
+            }
+        }
+    }
+    if (acc_r == 0) {  // uniform: the slot tables, k_small_finish follows
         if (sl != 0) return;
+        const size_t slot = (size_t)c * lp + j;
+        skeys[slot] = live ? top : 0ull;
+        sfhi[slot] = live ? st.x : 0u;
+        sub[slot] = live ? st.y : 0u;
+        return;
+    }
+    // One launch: fold into replica c % acc_r of the per-lane accumulators (skeys / sfhi / sub are then [acc_r][lp],
+    // all zero between launches) by no-return agent-scope atomic maxima, each array lane-contiguous so that a wave's
+    // instruction covers 512 / 256 contiguous bytes; idle lanes add nothing, sub only what is set. Then the arrival
+    // hand-off in its counter form: every wave drains its atomics, workgroup barrier, one returned add on the ticket;
+    // no workgroup waits for another, whatever the residency. The workgroup that draws the last ticket finishes.
+    if (sl == 0 && live) {
+        const size_t at = (size_t)(c % acc_r) * lp + j;
+        __hip_atomic_fetch_max(skeys + at, top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_max(sfhi + at, st.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (st.y) __hip_atomic_fetch_max(sub + at, st.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // also: slice 0 has read every other slice's lk / ls
+    if (threadIdx.x == 0)
+        lk[0] = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.y - 1u;
+    __syncthreads();
+    if (lk[0] == 0ull) return;  // uniform
+    // The finisher: one agent-scope acquire for the workgroup, then every accumulator word is read and reset in one
+    // returned agent-scope exchange (atomics both sides of the hand-off), folded over the replicas per lane through
+    // LDS, and every row takes its lane's result as k_small_finish writes it. The ticket goes back to zero too.
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // also: every thread has read the verdict in lk[0]
+    top = 0;
+    st = make_uint2(0u, 0u);
+    if (live) {
+#pragma unroll 4
+        for (uint32_t r = sl; r < acc_r; r += slices) {
+            const size_t at = (size_t)r * lp + j;
+            const uint64_t k2 = __hip_atomic_exchange(skeys + at, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t f2 = __hip_atomic_exchange(sfhi + at, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t u2 = __hip_atomic_exchange(sub + at, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            top = k2 > top ? k2 : top;
+            st.x = max(st.x, f2);
+            st.y = max(st.y, u2);
+        }
+    }
+    lk[threadIdx.x] = top;
+    ls[threadIdx.x] = st;
+    __syncthreads();
+    if (sl == 0) {
         for (uint32_t s2 = 1; s2 < slices; s2++) {
             const uint64_t k2 = lk[s2 * lp + j];
             const uint2 t2 = ls[s2 * lp + j];
@@ -407,11 +474,16 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
             st.y = max(st.y, t2.y);
             top = k2 > top ? k2 : top;
         }
+        // bit 0 of the status word: KG_ST_UNSUPPORTED when an unsupported pair's bound reaches the best fast key
+        ls[j] = make_uint2(st.y != 0u && st.y > st.x ? KG_ST_UNSUPPORTED : 0u, 0u);
+        lk[j] = top;
     }
-    const size_t slot = (size_t)c * lp + j;
-    skeys[slot] = live ? top : 0ull;
-    sfhi[slot] = live ? st.x : 0u;
-    sub[slot] = live ? st.y : 0u;
+    __syncthreads();
+    for (uint32_t r = threadIdx.x; r < n_rows; r += blockDim.x) {
+        const uint32_t l = lane_of[r];
+        out[r] = lk[l];
+        pstat[r] = ls[l].x;
+    }
 }
 
 // Second and last launch of the one-pod-block select: per row j of [0, n) the maximum key and the status over the
@@ -1264,7 +1336,8 @@ static void select_fast(const LaunchSelect& a, const SelectRange& r, hipStream_t
     }
 }
 
-// LaunchSelect.small: k_select_small over both classes' chunks, then k_small_finish over the rows
+// LaunchSelect.small: k_select_small over both classes' chunks, finishing inside the launch (small_replicas > 0) or
+// followed by k_small_finish over the rows
 static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
     const uint32_t lp = (a.n_fast + 63) / 64 * 64;
     const SelectRange &r0 = a.range[0], &r1 = a.range[1];
@@ -1272,7 +1345,8 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
     if (a.k != 1 || !a.fused || a.n_fast == 0 || a.n_fast != a.n_pods || lp > 256 || nc == 0 || nc > SMALL_MAX_CHUNKS ||
         (r0.n_chunks && (r0.chunk == 0 || r0.chunk > SMALL_MAX_CHUNK)) ||
         (r1.n_chunks && (r1.chunk == 0 || r1.chunk > SMALL_MAX_CHUNK)) || a.small_slices == 0 ||
-        a.small_slices * lp > SMALL_WG || !a.skeys || !a.sub || !a.sfhi || !a.lane_of)
+        a.small_slices * lp > SMALL_WG || !a.skeys || !a.sub || !a.sfhi || !a.lane_of ||
+        (a.small_replicas && !a.sticket))
         return hipErrorInvalidValue;
     dim3 grid(1, nc), block(lp * a.small_slices);
 #define KG_SMALL(PMV)                                                                                                 \
@@ -1280,11 +1354,13 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
         if (block.x <= 512u)                                                                                          \
             k_select_small<PMV, 512><<<grid, block, 0, s>>>(a.nodes, a.zones, a.pods, a.n_fast, lp, r0.end, r1.end,   \
                                                             r0.chunk, r1.chunk, r1.n_chunks, a.index_base, a.cfg,     \
-                                                            a.skeys, a.sub, a.sfhi, a.order);                         \
+                                                            a.skeys, a.sub, a.sfhi, a.order, a.small_replicas,        \
+                                                            a.sticket, a.lane_of, a.n_rows, a.out, a.pstat);          \
         else                                                                                                          \
             k_select_small<PMV, 1024><<<grid, block, 0, s>>>(a.nodes, a.zones, a.pods, a.n_fast, lp, r0.end, r1.end,  \
                                                              r0.chunk, r1.chunk, r1.n_chunks, a.index_base, a.cfg,    \
-                                                             a.skeys, a.sub, a.sfhi, a.order);                        \
+                                                             a.skeys, a.sub, a.sfhi, a.order, a.small_replicas,       \
+                                                             a.sticket, a.lane_of, a.n_rows, a.out, a.pstat);         \
     } while (0)
     switch (a.cfg.plugins & 7u) {
         case 0: KG_SMALL(0); break;
@@ -1297,8 +1373,9 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
         default: KG_SMALL(7); break;
     }
 #undef KG_SMALL
-    k_small_finish<<<dim3((a.n_rows + SMALL_FIN_WG - 1) / SMALL_FIN_WG), SMALL_FIN_WG, 0, s>>>(
-        a.skeys, a.sub, a.sfhi, nc, lp, a.n_fast, a.lane_of, a.n_rows, a.out, a.pstat);
+    if (a.small_replicas == 0)
+        k_small_finish<<<dim3((a.n_rows + SMALL_FIN_WG - 1) / SMALL_FIN_WG), SMALL_FIN_WG, 0, s>>>(
+            a.skeys, a.sub, a.sfhi, nc, lp, a.n_fast, a.lane_of, a.n_rows, a.out, a.pstat);
     return KG_LAUNCH_CHECK();
 }
 

@@ -231,6 +231,10 @@ struct kg_pods {
     uint32_t* d_ipair_count = nullptr;
     size_t ipairs_cap = 0;
     size_t partial_cap = 0;  // entries
+    // accumulators and ticket of the one-launch one-pod-block select: all zero between selects (ensure_sacc)
+    uint8_t* d_sacc = nullptr;
+    size_t sacc_cap = 0;  // bytes
+    bool sacc_dirty = false;
     uint64_t* d_keys = nullptr;
     uint32_t k_last = 0, kk_last = 0;
     uint64_t* h_keys = nullptr;    // pinned download staging of the keys [cap][KG_TOPK_MAX]
@@ -1671,7 +1675,7 @@ kg_status kg_pods_destroy(kg_pods* p) {
     hipStreamSynchronize(p->ctx->stream);
     if (p->ctx->side) hipStreamSynchronize(p->ctx->side);  // a plain-pod select may still read the batch there
     if (p->ctx->side2) hipStreamSynchronize(p->ctx->side2);  // and a class-1 lane of the config-5 kernels
-    for (void* b : {(void*)p->d_ipairs, (void*)p->d_ipair_count})
+    for (void* b : {(void*)p->d_ipairs, (void*)p->d_ipair_count, (void*)p->d_sacc})
         hipFree(b);
     for (void* b : {(void*)p->d_in, (void*)p->d_keys, (void*)p->d_winners, (void*)p->d_step, (void*)p->d_partial,
                     (void*)p->d_gather, (void*)p->d_qst, (void*)p->d_dev_max, (void*)p->d_rsv_max, (void*)p->d_pref,
@@ -2411,6 +2415,18 @@ static uint32_t device_cus(kg_ctx* ctx) {
 // threads that the copies of the lanes may fill (512: the launch-bound variant without scratch; 1024: the spilling one)
 constexpr uint32_t SMALL_COPIES_WG = 1024, SMALL_BIG_DEN = 250;
 constexpr uint32_t SMALL_MIN_CHUNK = 8, SMALL_FILL_NUM = 7, SMALL_FILL_DEN = 8;
+// The finish inside the launch: the workgroups fold into SMALL_REPLICAS replicas of the accumulators, whatever the chunk
+// count. Measured (tools/small_select_ab.py --replicas, profiles/small_fused/replicas_*.jsonl, ms per select by replica
+// count 1 / 4 / 8 / 16 / 32 / 64 / one per chunk, then the two launches): config 2 at 145 lanes (223 chunks) 0.0185 /
+// 0.0176 / 0.0182 / 0.0185 / 0.0197 / 0.0221 / 0.0343, two launches 0.0248; 64 lanes 0.0134 / 0.0120 / 0.0120 / 0.0122 /
+// 0.0126 / 0.0135 / 0.0178, 0.0151; 256 lanes 0.0191 / 0.0190 / 0.0197 / 0.0204 / 0.0220 / 0.0254 / 0.0422, 0.0303;
+// config 4's 100,000 nodes at 145 lanes (1,667 chunks) 0.1350 / 0.1332 / 0.1333 / 0.1337 / 0.1349 / 0.1381 / 0.2615,
+// 0.1798. Hundreds of workgroups adding to one address cost under 0.001 ms; every replica more is read by the lone
+// finisher. KG_SMALL_REPLICAS (read per call) sets the count, also past the row gate: the tool and the tests.
+// Row gate (--rows, profiles/small_fused/rows_breakeven.jsonl; 145 lanes, one launch / two launches): 10,000 rows
+// 0.0180 / 0.0250 ms, 50,000 rows 0.0259 / 0.0248, 200,000 rows 0.0558 / 0.0252: the lone finisher writes n_rows x 12
+// bytes, the break-even interpolates to about 45,000 rows, the one launch is taken up to SMALL_FUSED_MAX_ROWS.
+constexpr uint32_t SMALL_REPLICAS = 4, SMALL_FUSED_MAX_ROWS = 32768;
 static bool select_small(const kg_snap* s, LaunchSelect& a) {
     if (a.k != 1 || !a.fused || a.n_fast == 0 || a.n_fast != a.n_pods || a.n_fast > 256) return false;
     if (std::getenv("KG_NO_SMALL_SELECT")) return false;
@@ -2450,7 +2466,48 @@ static bool select_small(const kg_snap* s, LaunchSelect& a) {
     a.range[0] = r[0];
     a.range[1] = r[1];
     a.small = true;
+    // The finish inside the launch (small_replicas > 0), unless KG_NO_SMALL_FUSED_FINISH (read per call) or the row
+    // count keeps the two launches: a lone finisher writes all n_rows x 12 bytes.
+    const uint32_t nc = r[0].n_chunks + r[1].n_chunks;
+    a.small_replicas = 0;
+    if (!std::getenv("KG_NO_SMALL_FUSED_FINISH")) {
+        uint32_t rep = a.n_rows <= SMALL_FUSED_MAX_ROWS ? SMALL_REPLICAS : 0u;
+        if (const char* e = std::getenv("KG_SMALL_REPLICAS")) {  // also past the row gate
+            unsigned v = 0;
+            if (std::sscanf(e, "%u", &v) == 1 && v >= 1) rep = v;
+        }
+        a.small_replicas = std::min(rep, nc);  // more replicas than chunks: one chunk each
+    }
     return true;
+}
+
+// The accumulators and the ticket of the one-launch form (LaunchSelect.skeys / sfhi / sub / sticket): a buffer of
+// the batch's own, the ticket on the first 128-byte line, then [replicas][lp] keys, fast-key high words, unsupported
+// bounds. INVARIANT: every word is zero whenever no select runs on the batch. The memset below establishes it when the
+// buffer is allocated or regrown, and again before the first select after one that returned an error (sacc_dirty);
+// k_select_small's finisher reads every accumulator word by an exchange with zero and stores zero to the ticket, so a
+// steady-state step zeroes nothing from the host. All words being zero, the next launch may lay the arrays out for
+// another replica or lane count.
+constexpr size_t SACC_HEAD = 128;
+static kg_status ensure_sacc(kg_pods* p, uint32_t replicas, uint32_t lp) {
+    kg_ctx* ctx = p->ctx;
+    const size_t need = SACC_HEAD + (size_t)replicas * lp * 16;
+    if (need > p->sacc_cap) {
+        if (p->d_sacc) {
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipFree(p->d_sacc));
+            p->d_sacc = nullptr;
+            p->sacc_cap = 0;
+        }
+        HIP_TRY(ctx, hipMalloc(&p->d_sacc, need));
+        p->sacc_cap = need;
+        p->sacc_dirty = true;
+    }
+    if (p->sacc_dirty) {
+        HIP_TRY(ctx, hipMemsetAsync(p->d_sacc, 0, p->sacc_cap, ctx->stream));
+        p->sacc_dirty = false;
+    }
+    return KG_OK;
 }
 
 static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_out) {
@@ -2514,19 +2571,37 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     LaunchSelect a = make_select(s, p->dev, dd ? p->d_rorder : p->d_order, dd ? p->n_rep : p->n,
                                  dd ? p->n_rep_fast : p->n_fast, p->n, kk, true, d_out, nullptr, p->d_pstat, &parts);
     if (select_small(s, a)) {
-        // two launches write every row of d_out and d_pstat: no memset, no side stream, no expansion
-        const size_t slots = (size_t)(a.range[0].n_chunks + a.range[1].n_chunks) * ((a.n_fast + 63) / 64 * 64);
-        kg_status st = ensure_partial(p, 2 * slots);
-        if (st != KG_OK) return st;
-        a.skeys = p->d_partial;
-        a.sub = reinterpret_cast<uint32_t*>(p->d_partial + slots);
-        a.sfhi = a.sub + slots;
+        // one launch (or two) writes every row of d_out and d_pstat: no memset, no side stream, no expansion
+        const uint32_t lp = (a.n_fast + 63) / 64 * 64;
+        kg_status st;
+        if (a.small_replicas) {
+            st = ensure_sacc(p, a.small_replicas, lp);
+            if (st != KG_OK) return st;
+            const size_t slots = (size_t)a.small_replicas * lp;
+            a.sticket = reinterpret_cast<uint32_t*>(p->d_sacc);
+            a.skeys = reinterpret_cast<uint64_t*>(p->d_sacc + SACC_HEAD);
+            a.sfhi = reinterpret_cast<uint32_t*>(a.skeys + slots);
+            a.sub = a.sfhi + slots;
+        } else {
+            const size_t slots = (size_t)(a.range[0].n_chunks + a.range[1].n_chunks) * lp;
+            st = ensure_partial(p, 2 * slots);
+            if (st != KG_OK) return st;
+            a.skeys = p->d_partial;
+            a.sub = reinterpret_cast<uint32_t*>(p->d_partial + slots);
+            a.sfhi = a.sub + slots;
+        }
         a.lane_of = dd ? p->d_rlane : p->d_lane;
         hipEvent_t e0, e1;
         st = record_begin(ctx, &e0, &e1);
-        if (st != KG_OK) return st;
-        HIP_TRY(ctx, launch_select(a, ctx->stream));
-        return record_end(ctx, e0, e1);
+        if (st == KG_OK) {
+            const hipError_t le = launch_select(a, ctx->stream);
+            st = le == hipSuccess ? record_end(ctx, e0, e1)
+                                  : fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR,
+                                         "launch_select(a, ctx->stream): %s", hipGetErrorString(le));
+        }
+        // a failed call may have left a launch half done: the accumulators are zeroed again before the next one
+        if (st != KG_OK && a.small_replicas) p->sacc_dirty = true;
+        return st;
     }
     HIP_TRY(ctx, hipMemsetAsync(p->d_pstat, 0, sizeof(uint32_t) * p->n, ctx->stream));
     kg_status st = ensure_partial(p, std::max<size_t>((size_t)parts * p->n * kk, 1));

@@ -1,17 +1,23 @@
 #!/usr/bin/env python3
-"""A/B aid for the one-pod-block fused top-1 select (k_select_small + k_small_finish; select_small in kg_runtime.cpp)
-under bench.py's warm-up and step counts. It imports the package of the tree it lies in.
+"""A/B aid for the one-pod-block fused top-1 select (k_select_small, finishing in its own launch or followed by
+k_small_finish; select_small in kg_runtime.cpp) under bench.py's warm-up and step counts. It imports the package of the tree it lies in.
 
 Default: config 2's pods (145 distinct rows of 10,000) against config 2's nodes and against synth.mixed()'s nodes,
 which hold many F_BIG records (Restricted nodes, node CPU bind policies: the records the new path evaluates inline
-instead of in k_big_sel), each timed on the new path and with KG_NO_SMALL_SELECT=1 in the same process, alternating;
-the keys of the two paths are compared once per snapshot.
+instead of in k_big_sel), each timed on the one-launch path, with KG_NO_SMALL_FUSED_FINISH=1 (the two launches) and
+with KG_NO_SMALL_SELECT=1 (the general path) in the same process, alternating; the keys of the paths are compared once
+per snapshot.
 
 --sweep "c0,c1,copies;...": the new path under KG_SMALL_CHUNKS settings (records per workgroup of storage class 0 / 1,
 lane copies per workgroup: up to 512 threads run the launch-bound variant without scratch), what select_small's
 geometry is set from.
 --nodes also takes config4 (100,000 nodes).
 --lanes N: N all-distinct pods instead of config 2's (the launch then has N lanes, no pod-row reduction).
+--rows N: config 2's pods tiled to N rows (the same distinct rows: the lane count stays, the finish writes N rows), for
+the row gate of the one-launch finish in select_small.
+--replicas "1,4,...,all,two": the one-launch path under KG_SMALL_REPLICAS settings ("all": one replica per chunk, no two
+workgroups share an address; "two": KG_NO_SMALL_FUSED_FINISH=1, the two launches, as the yardstick), what select_small's
+replica rule is set from.
 --shares "0,0.02,...": synth.mixed()'s nodes thinned to these F_BIG shares (every other node kept, the first F_BIG
 nodes up to the share), for the break-even of the F_BIG gate in select_small. KG_SMALL_ALLOW_BIG=1 (set here) lifts
 that gate so that both paths can be timed above it.
@@ -36,6 +42,8 @@ def main():
     ap.add_argument("--nodes", default="config2,mixed")
     ap.add_argument("--sweep", default=None)
     ap.add_argument("--lanes", type=int, default=0)
+    ap.add_argument("--rows", type=int, default=0)
+    ap.add_argument("--replicas", default=None)
     ap.add_argument("--shares", default=None)
     ap.add_argument("--chunks", default=None, help="KG_SMALL_CHUNKS for the new path's side of the A/B")
     a = ap.parse_args()
@@ -48,6 +56,8 @@ def main():
     if a.lanes:
         pods = abi.take(pods, np.arange(a.lanes))
         pods["req_eph"] = (pods["req_eph"] + np.arange(a.lanes)).astype(np.int64)
+    if a.rows:
+        pods = abi.take(pods, np.arange(a.rows) % abi.table_len(pods))
     ctx = engine.Context(0)
     batch = engine.PodBatch(ctx, pods)
     lanes = batch.select_lanes()
@@ -91,19 +101,32 @@ def main():
         snap = engine.Snapshot(ctx, cfg.kg_config(), nodes)
         keys = engine.eval_select(snap, batch, 1)
         keys0 = with_env("KG_NO_SMALL_SELECT", "1", lambda: engine.eval_select(snap, batch, 1))
+        keys2 = with_env("KG_NO_SMALL_FUSED_FINISH", "1", lambda: engine.eval_select(snap, batch, 1))
         head = {"nodes": name, "n_nodes": abi.table_len(nodes), "f_big_share": float(big.mean()), "pods": batch.n,
                 "lanes": lanes[0], "fast_lanes": lanes[1], "steps": a.steps, "warmup": a.warmup,
-                "keys_equal": bool(np.array_equal(keys, keys0)), "feasible_rows": int((keys != 0).sum())}
+                "keys_equal": bool(np.array_equal(keys, keys0)), "keys_equal_two_launch": bool(np.array_equal(keys, keys2)),
+                "feasible_rows": int((keys != 0).sum())}
+
+        def time_replicas(r):
+            if r == "two":
+                return with_env("KG_NO_SMALL_FUSED_FINISH", "1", lambda: time_select(snap))
+            return with_env("KG_SMALL_REPLICAS", "4096" if r == "all" else r, lambda: time_select(snap))
+
         for rep in range(a.repeat):
-            if a.sweep:
+            if a.replicas:
+                for r in a.replicas.split(","):
+                    ms = with_env("KG_SMALL_CHUNKS", a.chunks, lambda: time_replicas(r)) if a.chunks else time_replicas(r)
+                    print(json.dumps(dict(head, repeat=rep, chunks=a.chunks, replicas=r, select_ms_small=ms)), flush=True)
+            elif a.sweep:
                 for setting in a.sweep.split(";"):
                     ms = with_env("KG_SMALL_CHUNKS", setting, lambda: time_select(snap))
                     print(json.dumps(dict(head, repeat=rep, chunks=setting, select_ms_small=ms)), flush=True)
             else:
                 small = with_env("KG_SMALL_CHUNKS", a.chunks, lambda: time_select(snap)) if a.chunks else time_select(snap)
+                two = with_env("KG_NO_SMALL_FUSED_FINISH", "1", lambda: time_select(snap))
                 general = with_env("KG_NO_SMALL_SELECT", "1", lambda: time_select(snap))
-                print(json.dumps(dict(head, repeat=rep, chunks=a.chunks, select_ms_small=small, select_ms_general=general)),
-                      flush=True)
+                print(json.dumps(dict(head, repeat=rep, chunks=a.chunks, select_ms_small=small, select_ms_two_launch=two,
+                                      select_ms_general=general)), flush=True)
         snap.close()
     batch.close()
     ctx.close()
