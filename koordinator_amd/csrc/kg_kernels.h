@@ -68,6 +68,10 @@ struct LaunchSelect {
     uint32_t small_slices;   // waves sets per workgroup, each walking its part of the workgroup's chunk
     uint32_t small_replicas;  // replicas of the accumulators; they and *sticket are zero before and after every launch
     uint32_t* sticket;        // arrival counter of the launch
+    // optional timing pair of the small select (both set, or neither): the launch binds ev_start to k_select_small's
+    // begin and ev_stop to the end of the kernel that finishes the step (hipExtLaunchKernelGGL), instead of the caller
+    // recording events around it. Bound only when launch_select returns hipSuccess
+    hipEvent_t ev_start, ev_stop;
 };
 constexpr uint32_t SMALL_MAX_CHUNK = 64, SMALL_MAX_CHUNKS = 4096;
 constexpr uint32_t SMALL_WG = 1024;  // most threads of a k_select_small workgroup

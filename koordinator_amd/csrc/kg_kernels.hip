@@ -18,6 +18,7 @@
 //              winning node in place, evaluates the pod on every node, block max -> atomicMax.
 //   k_assume   Reserve / Unreserve of one pod on one node.
 // No MFMA: this is integer / IEEE-double scalar work bound by VALU issue and on-chip bandwidth.
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include "kg_eval.h"
@@ -1337,7 +1338,10 @@ static void select_fast(const LaunchSelect& a, const SelectRange& r, hipStream_t
 }
 
 // LaunchSelect.small: k_select_small over both classes' chunks, finishing inside the launch (small_replicas > 0) or
-// followed by k_small_finish over the rows
+// followed by k_small_finish over the rows. With a.ev_start and a.ev_stop both set the kernels go through
+// hipExtLaunchKernelGGL, which binds the events to the dispatch's own begin and end timestamps: the start event to
+// k_select_small, the stop event to the kernel that ends the step. Nothing is recorded on the stream. Without them the
+// launch is the plain <<<>>> one.
 static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
     const uint32_t lp = (a.n_fast + 63) / 64 * 64;
     const SelectRange &r0 = a.range[0], &r1 = a.range[1];
@@ -1349,18 +1353,25 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
         (a.small_replicas && !a.sticket))
         return hipErrorInvalidValue;
     dim3 grid(1, nc), block(lp * a.small_slices);
+    const bool timed = a.ev_start && a.ev_stop;
+    const hipEvent_t sel_stop = a.small_replicas ? a.ev_stop : nullptr;  // two launches: k_small_finish ends the step
+#define KG_SMALL_ARGS                                                                                                 \
+    a.nodes, a.zones, a.pods, a.n_fast, lp, r0.end, r1.end, r0.chunk, r1.chunk, r1.n_chunks, a.index_base, a.cfg,      \
+        a.skeys, a.sub, a.sfhi, a.order, a.small_replicas, a.sticket, a.lane_of, a.n_rows, a.out, a.pstat
+#define KG_SMALL_WG(PMV, WGV)                                                                                         \
+    do {                                                                                                              \
+        if (timed)                                                                                                    \
+            hipExtLaunchKernelGGL((k_select_small<PMV, WGV>), grid, block, 0, s, a.ev_start, sel_stop, 0,             \
+                                  KG_SMALL_ARGS);                                                                     \
+        else                                                                                                          \
+            k_select_small<PMV, WGV><<<grid, block, 0, s>>>(KG_SMALL_ARGS);                                           \
+    } while (0)
 #define KG_SMALL(PMV)                                                                                                 \
     do {                                                                                                              \
         if (block.x <= 512u)                                                                                          \
-            k_select_small<PMV, 512><<<grid, block, 0, s>>>(a.nodes, a.zones, a.pods, a.n_fast, lp, r0.end, r1.end,   \
-                                                            r0.chunk, r1.chunk, r1.n_chunks, a.index_base, a.cfg,     \
-                                                            a.skeys, a.sub, a.sfhi, a.order, a.small_replicas,        \
-                                                            a.sticket, a.lane_of, a.n_rows, a.out, a.pstat);          \
+            KG_SMALL_WG(PMV, 512);                                                                                    \
         else                                                                                                          \
-            k_select_small<PMV, 1024><<<grid, block, 0, s>>>(a.nodes, a.zones, a.pods, a.n_fast, lp, r0.end, r1.end,  \
-                                                             r0.chunk, r1.chunk, r1.n_chunks, a.index_base, a.cfg,    \
-                                                             a.skeys, a.sub, a.sfhi, a.order, a.small_replicas,       \
-                                                             a.sticket, a.lane_of, a.n_rows, a.out, a.pstat);         \
+            KG_SMALL_WG(PMV, 1024);                                                                                   \
     } while (0)
     switch (a.cfg.plugins & 7u) {
         case 0: KG_SMALL(0); break;
@@ -1373,9 +1384,18 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
         default: KG_SMALL(7); break;
     }
 #undef KG_SMALL
-    if (a.small_replicas == 0)
-        k_small_finish<<<dim3((a.n_rows + SMALL_FIN_WG - 1) / SMALL_FIN_WG), SMALL_FIN_WG, 0, s>>>(
-            a.skeys, a.sub, a.sfhi, nc, lp, a.n_fast, a.lane_of, a.n_rows, a.out, a.pstat);
+#undef KG_SMALL_WG
+#undef KG_SMALL_ARGS
+    if (a.small_replicas == 0) {
+        const dim3 fgrid((a.n_rows + SMALL_FIN_WG - 1) / SMALL_FIN_WG);
+        if (timed)
+            hipExtLaunchKernelGGL(k_small_finish, fgrid, dim3(SMALL_FIN_WG), 0, s, (hipEvent_t) nullptr, a.ev_stop, 0,
+                                  (const uint64_t*)a.skeys, (const uint32_t*)a.sub, (const uint32_t*)a.sfhi, nc, lp, a.n_fast,
+                                  a.lane_of, a.n_rows, a.out, a.pstat);
+        else
+            k_small_finish<<<fgrid, SMALL_FIN_WG, 0, s>>>(a.skeys, a.sub, a.sfhi, nc, lp, a.n_fast, a.lane_of, a.n_rows,
+                                                          a.out, a.pstat);
+    }
     return KG_LAUNCH_CHECK();
 }
 

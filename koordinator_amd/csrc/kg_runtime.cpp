@@ -764,18 +764,41 @@ void place_records(kg_snap* s, std::vector<NodeRec>& recs, std::vector<ZoneRec>&
     count_topo(s);
 }
 
-kg_status record_begin(kg_ctx* ctx, hipEvent_t* a, hipEvent_t* b) {
+// A pair of timing events from the context's pool (both nullptr with profiling off), recorded nowhere yet. The caller
+// either gets both onto the stream and puts the pair on ev_live, or hands it back with bracket_drop: a pair on ev_live
+// that was never recorded or bound would fail kg_profile_read.
+kg_status bracket_take(kg_ctx* ctx, hipEvent_t* a, hipEvent_t* b) {
     *a = *b = nullptr;
     if (!ctx->profiling) return KG_OK;
     if (!ctx->ev_free.empty()) {
         *a = ctx->ev_free.back().first;
         *b = ctx->ev_free.back().second;
         ctx->ev_free.pop_back();
-    } else {
-        HIP_TRY(ctx, hipEventCreate(a));
-        HIP_TRY(ctx, hipEventCreate(b));
+        return KG_OK;
     }
-    HIP_TRY(ctx, hipEventRecord(*a, ctx->stream));
+    HIP_TRY(ctx, hipEventCreate(a));
+    const hipError_t e = hipEventCreate(b);
+    if (e != hipSuccess) {
+        hipEventDestroy(*a);
+        *a = *b = nullptr;
+        HIP_TRY(ctx, e);
+    }
+    return KG_OK;
+}
+
+void bracket_drop(kg_ctx* ctx, hipEvent_t a, hipEvent_t b) {
+    if (a) ctx->ev_free.emplace_back(a, b);
+}
+
+kg_status record_begin(kg_ctx* ctx, hipEvent_t* a, hipEvent_t* b) {
+    kg_status st = bracket_take(ctx, a, b);
+    if (st != KG_OK || !*a) return st;
+    const hipError_t e = hipEventRecord(*a, ctx->stream);
+    if (e != hipSuccess) {
+        bracket_drop(ctx, *a, *b);
+        *a = *b = nullptr;
+        HIP_TRY(ctx, e);
+    }
     return KG_OK;
 }
 
@@ -2591,13 +2614,19 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
             a.sfhi = a.sub + slots;
         }
         a.lane_of = dd ? p->d_rlane : p->d_lane;
-        hipEvent_t e0, e1;
-        st = record_begin(ctx, &e0, &e1);
+        // kernel-time bracket (kg_profile_read): the launch carries the pair itself (LaunchSelect.ev_start / ev_stop),
+        // nothing is recorded on the stream around a kernel of some 18 us. The pair goes on ev_live only
+        // once the launch took it; every failure hands it back to the pool
+        st = bracket_take(ctx, &a.ev_start, &a.ev_stop);
         if (st == KG_OK) {
             const hipError_t le = launch_select(a, ctx->stream);
-            st = le == hipSuccess ? record_end(ctx, e0, e1)
-                                  : fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR,
-                                         "launch_select(a, ctx->stream): %s", hipGetErrorString(le));
+            if (le != hipSuccess) {
+                bracket_drop(ctx, a.ev_start, a.ev_stop);
+                st = fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR, "launch_select(a, ctx->stream): %s",
+                          hipGetErrorString(le));
+            } else if (a.ev_start) {
+                ctx->ev_live.emplace_back(a.ev_start, a.ev_stop);
+            }
         }
         // a failed call may have left a launch half done: the accumulators are zeroed again before the next one
         if (st != KG_OK && a.small_replicas) p->sacc_dirty = true;

@@ -18,6 +18,8 @@ the row gate of the one-launch finish in select_small.
 --replicas "1,4,...,all,two": the one-launch path under KG_SMALL_REPLICAS settings ("all": one replica per chunk, no two
 workgroups share an address; "two": KG_NO_SMALL_FUSED_FINISH=1, the two launches, as the yardstick), what select_small's
 replica rule is set from.
+--profile: the timed loop runs with the profile bracket on, as bench.py's does; every line also carries the host time of
+the submission loop alone (submit_ms_small: per call, before the final sync) and the bracket's device time per select.
 --shares "0,0.02,...": synth.mixed()'s nodes thinned to these F_BIG shares (every other node kept, the first F_BIG
 nodes up to the share), for the break-even of the F_BIG gate in select_small. KG_SMALL_ALLOW_BIG=1 (set here) lifts
 that gate so that both paths can be timed above it.
@@ -46,6 +48,8 @@ def main():
     ap.add_argument("--replicas", default=None)
     ap.add_argument("--shares", default=None)
     ap.add_argument("--chunks", default=None, help="KG_SMALL_CHUNKS for the new path's side of the A/B")
+    ap.add_argument("--profile", action="store_true",
+                    help="time with the profile bracket on (ctx.profile, as bench.py does) and report the bracket")
     a = ap.parse_args()
 
     import numpy as np
@@ -62,15 +66,29 @@ def main():
     batch = engine.PodBatch(ctx, pods)
     lanes = batch.select_lanes()
 
+    last = {}  # of the latest time_select: host time of the submission loop alone, and the profile bracket
+
     def time_select(snap):
         for _ in range(a.warmup):
             engine.eval_select_async(snap, batch, 1)
         ctx.sync()
+        if a.profile:  # as bench.py does around its timed steps
+            ctx.profile(True)
+            ctx.profile_read(reset=True)
+            ctx.sync()
         t0 = time.perf_counter()
         for _ in range(a.steps):
             engine.eval_select_async(snap, batch, 1)
+        t1 = time.perf_counter()
         ctx.sync()
-        return (time.perf_counter() - t0) / a.steps * 1e3
+        t2 = time.perf_counter()
+        last["submit_ms"] = (t1 - t0) / a.steps * 1e3
+        last["bracket_ms"] = None
+        if a.profile:
+            ms, n = ctx.profile_read(reset=True)
+            ctx.profile(False)
+            last["bracket_ms"] = ms / n if n else None
+        return (t2 - t0) / a.steps * 1e3
 
     def with_env(name, value, fn):
         os.environ[name] = value
@@ -116,17 +134,20 @@ def main():
             if a.replicas:
                 for r in a.replicas.split(","):
                     ms = with_env("KG_SMALL_CHUNKS", a.chunks, lambda: time_replicas(r)) if a.chunks else time_replicas(r)
-                    print(json.dumps(dict(head, repeat=rep, chunks=a.chunks, replicas=r, select_ms_small=ms)), flush=True)
+                    print(json.dumps(dict(head, repeat=rep, chunks=a.chunks, replicas=r, select_ms_small=ms,
+                                          profile=a.profile, submit_ms_small=last["submit_ms"],
+                                          bracket_ms_small=last["bracket_ms"])), flush=True)
             elif a.sweep:
                 for setting in a.sweep.split(";"):
                     ms = with_env("KG_SMALL_CHUNKS", setting, lambda: time_select(snap))
                     print(json.dumps(dict(head, repeat=rep, chunks=setting, select_ms_small=ms)), flush=True)
             else:
                 small = with_env("KG_SMALL_CHUNKS", a.chunks, lambda: time_select(snap)) if a.chunks else time_select(snap)
+                host = dict(profile=a.profile, submit_ms_small=last["submit_ms"], bracket_ms_small=last["bracket_ms"])
                 two = with_env("KG_NO_SMALL_FUSED_FINISH", "1", lambda: time_select(snap))
                 general = with_env("KG_NO_SMALL_SELECT", "1", lambda: time_select(snap))
                 print(json.dumps(dict(head, repeat=rep, chunks=a.chunks, select_ms_small=small, select_ms_two_launch=two,
-                                      select_ms_general=general)), flush=True)
+                                      select_ms_general=general, **host)), flush=True)
         snap.close()
     batch.close()
     ctx.close()
