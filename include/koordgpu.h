@@ -745,7 +745,11 @@ kg_status kg_snapshot_rollback(kg_snap* snap);
 kg_status kg_batch_schedule(kg_snap* snap, kg_pods* pods, const int32_t* plan_node, uint32_t* out_result,
                             uint32_t* out_status, int32_t* out_zone, uint32_t* out_minors);
 
-/* Timing of the dominant kernel with HIP events on the launch stream. */
+/* Device time of the select / replay steps: one bracket per step, summed. A step of several device operations is
+ * bracketed by HIP events on the launch stream. The one-launch top-1 select of one pod block times
+ * itself with the device's wall clock instead (hipDeviceAttributeWallClockRate): its bracket runs from the first
+ * workgroup's entry to the completion of the last row store, which leaves out the dispatch's launch ramp and
+ * end-of-kernel release (a few microseconds). kg_profile_read waits for the brackets still outstanding. */
 kg_status kg_profile_enable(kg_ctx* ctx, int enable);
 kg_status kg_profile_read(kg_ctx* ctx, double* total_ms, uint64_t* launches, int reset);
 

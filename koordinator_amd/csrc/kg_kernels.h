@@ -72,7 +72,15 @@ struct LaunchSelect {
     // begin and ev_stop to the end of the kernel that finishes the step (hipExtLaunchKernelGGL), instead of the caller
     // recording events around it. Bound only when launch_select returns hipSuccess
     hipEvent_t ev_start, ev_stop;
+    // or (one launch only, never together with the pair) the kernel times itself with the device clock: prof[0] += ticks
+    // from the first workgroup's entry to the finisher's last row store, prof[1] += 1. The begin word of the launch is
+    // the 64-bit word SMALL_BEGIN_WORD of sticket's 128-byte line: zero before and after every launch
+    uint64_t* prof;
+    // measurement aid (KG_SMALL_PHASES): prof is a scratch pair of the launch's own, followed by [chunks][4] clock
+    // readings per workgroup, see k_select_small
+    bool phases;
 };
+constexpr uint32_t SMALL_BEGIN_WORD = 8;  // in 64-bit words from sticket
 constexpr uint32_t SMALL_MAX_CHUNK = 64, SMALL_MAX_CHUNKS = 4096;
 constexpr uint32_t SMALL_WG = 1024;  // most threads of a k_select_small workgroup
 inline uint32_t select_fparts(const LaunchSelect& a) { return a.big_part0 + a.big_y; }

@@ -327,7 +327,17 @@ __global__ __launch_bounds__(256) KG_SEL1_ATTR void k_select1(const NodeRec* __r
 // wave-uniform and select1_loop keeps its wide scalar record loads. WG: the launch bound, 512 (up to 256 VGPRs: the
 // inline integer path fits without scratch) or 1024 (128 VGPRs: it spills; more copies per workgroup). The chunks are
 // dealt to the XCDs in contiguous runs (xcd_block; launch order measured the same).
-template <uint32_t PM, uint32_t WG>
+// prof (nullable; only with acc_r > 0): the launch times itself for kg_profile_read with the device-wide 100 MHz clock
+// (wall_clock64), so that the dispatch carries no event pair. Thread 0 of every workgroup folds the complement of its
+// entry time into the begin word (SMALL_BEGIN_WORD: on the ticket's line, zero between launches like every word of
+// that buffer; the maximum of the complements is the complement of the earliest entry), long before the drain and the ticket that
+// publish the accumulators, so they publish it too. The finisher takes the word back to zero with its other exchanges
+// and, once its row stores have completed, adds end - begin to prof[0] and 1 to prof[1]. With prof == nullptr the
+// kernel runs two uniform branches more and nothing else.
+// PH (KG_SMALL_PHASES, a measurement aid; off in every instantiation the library launches by default): prof is set and
+// the launch's own scratch pair, followed by four clock readings per workgroup that thread 0 stores: entry, loops done
+// (after the slices met in LDS), ticket drawn and, the finisher only (else zero), rows stored.
+template <uint32_t PM, uint32_t WG, bool PH = false>
 __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__ nodes, const ZoneRec* __restrict__ zones,
                                                            PodsDev pods, uint32_t n_lanes, uint32_t lp, uint32_t n0,
                                                            uint32_t n_end, uint32_t chunk0, uint32_t chunk1, uint32_t nc1,
@@ -336,9 +346,18 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
                                                            const uint32_t* __restrict__ order, uint32_t acc_r,
                                                            uint32_t* __restrict__ ticket,
                                                            const uint8_t* __restrict__ lane_of, uint32_t n_rows,
-                                                           uint64_t* __restrict__ out, uint32_t* __restrict__ pstat) {
+                                                           uint64_t* __restrict__ out, uint32_t* __restrict__ pstat,
+                                                           uint64_t* __restrict__ prof) {
     __shared__ uint64_t lk[WG];
     __shared__ uint2 ls[WG];
+    uint64_t ph_entry = 0, ph_loops = 0;
+    uint64_t* const pbegin = reinterpret_cast<uint64_t*>(ticket) + SMALL_BEGIN_WORD;
+    uint64_t* const phases = prof + 2;  // PH only
+    if (PH || prof) {  // uniform
+        const uint64_t t_in = wall_clock64();
+        if (PH) ph_entry = t_in;
+        if (prof && threadIdx.x == 0) __hip_atomic_fetch_max(pbegin, ~t_in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     const uint32_t c = xcd_block().y, slices = blockDim.x / lp;
     const uint32_t j = threadIdx.x % lp;
     const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / lp));  // lp is whole waves
@@ -429,6 +448,7 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
     // instruction covers 512 / 256 contiguous bytes; idle lanes add nothing, sub only what is set. Then the arrival
     // hand-off in its counter form: every wave drains its atomics, workgroup barrier, one returned add on the ticket;
     // no workgroup waits for another, whatever the residency. The workgroup that draws the last ticket finishes.
+    if (PH) ph_loops = wall_clock64();
     if (sl == 0 && live) {
         const size_t at = (size_t)(c % acc_r) * lp + j;
         __hip_atomic_fetch_max(skeys + at, top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -440,13 +460,22 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
     if (threadIdx.x == 0)
         lk[0] = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.y - 1u;
     __syncthreads();
+    if (PH && threadIdx.x == 0) {
+        uint64_t* slot = phases + (size_t)c * 4;
+        slot[0] = ph_entry;
+        slot[1] = ph_loops;
+        slot[2] = wall_clock64();
+        slot[3] = 0;
+    }
     if (lk[0] == 0ull) return;  // uniform
     // The finisher: one agent-scope acquire for the workgroup, then every accumulator word is read and reset in one
     // returned agent-scope exchange (atomics both sides of the hand-off), folded over the replicas per lane through
     // LDS, and every row takes its lane's result as k_small_finish writes it. The ticket goes back to zero too.
+    uint64_t t_begin = 0;
     if (threadIdx.x == 0) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (prof) t_begin = ~__hip_atomic_exchange(pbegin, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // also: every thread has read the verdict in lk[0]
@@ -484,6 +513,18 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
         const uint32_t l = lane_of[r];
         out[r] = lk[l];
         pstat[r] = ls[l].x;
+    }
+    if (PH || prof) {  // uniform: the bracket ends when every row store of the workgroup has completed
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint64_t t_end = wall_clock64();
+            if (PH) phases[(size_t)c * 4 + 3] = t_end;
+            if (prof) {
+                __hip_atomic_fetch_add(prof, t_end - t_begin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(prof + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
     }
 }
 
@@ -1341,7 +1382,8 @@ static void select_fast(const LaunchSelect& a, const SelectRange& r, hipStream_t
 // followed by k_small_finish over the rows. With a.ev_start and a.ev_stop both set the kernels go through
 // hipExtLaunchKernelGGL, which binds the events to the dispatch's own begin and end timestamps: the start event to
 // k_select_small, the stop event to the kernel that ends the step. Nothing is recorded on the stream. Without them the
-// launch is the plain <<<>>> one.
+// launch is the plain <<<>>> one. a.prof (one launch only): the kernel times itself, plain launch, no events. a.phases
+// (a.prof is then the launch's scratch pair in front of the readings): the PH instantiation, which exists for the plugin mask and launch bound of config 2 only.
 static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
     const uint32_t lp = (a.n_fast + 63) / 64 * 64;
     const SelectRange &r0 = a.range[0], &r1 = a.range[1];
@@ -1350,14 +1392,14 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
         (r0.n_chunks && (r0.chunk == 0 || r0.chunk > SMALL_MAX_CHUNK)) ||
         (r1.n_chunks && (r1.chunk == 0 || r1.chunk > SMALL_MAX_CHUNK)) || a.small_slices == 0 ||
         a.small_slices * lp > SMALL_WG || !a.skeys || !a.sub || !a.sfhi || !a.lane_of ||
-        (a.small_replicas && !a.sticket))
+        (a.small_replicas && !a.sticket) || (a.prof && (!a.small_replicas || a.ev_start || a.ev_stop)) || (a.phases && !a.prof))
         return hipErrorInvalidValue;
     dim3 grid(1, nc), block(lp * a.small_slices);
     const bool timed = a.ev_start && a.ev_stop;
     const hipEvent_t sel_stop = a.small_replicas ? a.ev_stop : nullptr;  // two launches: k_small_finish ends the step
 #define KG_SMALL_ARGS                                                                                                 \
     a.nodes, a.zones, a.pods, a.n_fast, lp, r0.end, r1.end, r0.chunk, r1.chunk, r1.n_chunks, a.index_base, a.cfg,      \
-        a.skeys, a.sub, a.sfhi, a.order, a.small_replicas, a.sticket, a.lane_of, a.n_rows, a.out, a.pstat
+        a.skeys, a.sub, a.sfhi, a.order, a.small_replicas, a.sticket, a.lane_of, a.n_rows, a.out, a.pstat, a.prof
 #define KG_SMALL_WG(PMV, WGV)                                                                                         \
     do {                                                                                                              \
         if (timed)                                                                                                    \
@@ -1373,6 +1415,10 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
         else                                                                                                          \
             KG_SMALL_WG(PMV, 1024);                                                                                   \
     } while (0)
+    if (a.phases) {
+        if ((a.cfg.plugins & 7u) != 7u || block.x <= 512u || !a.small_replicas || timed) return hipErrorInvalidValue;
+        k_select_small<7, 1024, true><<<grid, block, 0, s>>>(KG_SMALL_ARGS);
+    } else
     switch (a.cfg.plugins & 7u) {
         case 0: KG_SMALL(0); break;
         case 1: KG_SMALL(1); break;

@@ -44,6 +44,16 @@ struct kg_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
     double prof_ms = 0.0;
     uint64_t prof_launches = 0;
+    // The one-launch small select times itself (k_select_small's prof): d_prof = {tick sum, launch count}
+    // of the device's wall clock, allocated and zeroed at the first such select and never reset; prof_seen = the words at
+    // the last kg_profile_read; prof_pending = launches handed d_prof since then; clock_khz = that clock's rate
+    // (hipDeviceAttributeWallClockRate; -1: not queried yet, 0: not available, the bound event pair stays).
+    uint64_t* d_prof = nullptr;
+    uint64_t prof_seen[2] = {0, 0};
+    uint64_t prof_pending = 0;
+    int clock_khz = -1;
+    uint64_t* d_phases = nullptr;  // KG_SMALL_PHASES: per-workgroup clock readings of one launch (measurement aid)
+    size_t phases_cap = 0;
     int cus = -1;  // compute units of the device (device_cus), queried on first use
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
@@ -870,6 +880,8 @@ kg_status kg_close(kg_ctx* ctx) {
         hipEventDestroy(e.first);
         hipEventDestroy(e.second);
     }
+    if (ctx->d_prof) hipFree(ctx->d_prof);
+    if (ctx->d_phases) hipFree(ctx->d_phases);
     if (ctx->side) hipStreamDestroy(ctx->side);
     if (ctx->fork) hipEventDestroy(ctx->fork);
     if (ctx->join) hipEventDestroy(ctx->join);
@@ -2512,6 +2524,57 @@ static bool select_small(const kg_snap* s, LaunchSelect& a) {
 // steady-state step zeroes nothing from the host. All words being zero, the next launch may lay the arrays out for
 // another replica or lane count.
 constexpr size_t SACC_HEAD = 128;
+static_assert((SMALL_BEGIN_WORD + 1) * sizeof(uint64_t) <= SACC_HEAD, "the begin word of a launch that times itself "
+              "(LaunchSelect.prof) lies on the ticket's line, under the same invariant");
+
+// The context's device-clock counters (kg_ctx.d_prof) for a profiled one-launch select; *out stays nullptr when the
+// device reports no wall clock rate: the caller then keeps the bound event pair.
+static kg_status ensure_prof(kg_ctx* ctx, uint64_t** out) {
+    *out = nullptr;
+    if (ctx->clock_khz < 0) {
+        int khz = 0;
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ctx->device) != hipSuccess) khz = 0;
+        ctx->clock_khz = khz > 0 ? khz : 0;
+    }
+    if (ctx->clock_khz == 0) return KG_OK;
+    if (!ctx->d_prof) {
+        uint64_t* d = nullptr;
+        HIP_TRY(ctx, hipMalloc(&d, 2 * sizeof(uint64_t)));
+        const hipError_t e = hipMemsetAsync(d, 0, 2 * sizeof(uint64_t), ctx->stream);
+        if (e != hipSuccess) {
+            hipFree(d);
+            HIP_TRY(ctx, e);
+        }
+        ctx->d_prof = d;
+        ctx->prof_seen[0] = ctx->prof_seen[1] = 0;
+        ctx->prof_pending = 0;
+    }
+    *out = ctx->d_prof;
+    return KG_OK;
+}
+
+// KG_SMALL_PHASES=<file> (read per call; measurement aid, tools/small_select_ab.py --phases): the one-launch select of
+// config 2's shape (all three plugins, the 1,024-thread variant) runs k_select_small's PH instantiation; after the
+// launch the stream is synchronised and one record is appended to the file: uint64 workgroup count, then four uint64
+// clock readings per workgroup (entry, loops done, ticket drawn, rows stored or 0). Other shapes ignore the switch.
+static const char* small_phases_file(const LaunchSelect& a, uint32_t lp) {
+    const char* f = std::getenv("KG_SMALL_PHASES");
+    if (!f || !*f || !a.small_replicas || (a.cfg.plugins & 7u) != 7u || a.small_slices * lp <= 512u) return nullptr;
+    return f;
+}
+
+static kg_status small_phases_write(kg_ctx* ctx, const char* file, uint32_t nc) {
+    std::vector<uint64_t> h((size_t)nc * 4 + 1);
+    h[0] = nc;
+    HIP_TRY(ctx, hipMemcpyAsync(h.data() + 1, ctx->d_phases + 2, sizeof(uint64_t) * nc * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    FILE* fp = std::fopen(file, "ab");
+    if (!fp) return fail(ctx, KG_INVALID_ARG, "KG_SMALL_PHASES: cannot open %s", file);
+    const bool ok = std::fwrite(h.data(), sizeof(uint64_t), h.size(), fp) == h.size();
+    std::fclose(fp);
+    return ok ? KG_OK : fail(ctx, KG_INVALID_ARG, "KG_SMALL_PHASES: short write to %s", file);
+}
+
 static kg_status ensure_sacc(kg_pods* p, uint32_t replicas, uint32_t lp) {
     kg_ctx* ctx = p->ctx;
     const size_t need = SACC_HEAD + (size_t)replicas * lp * 16;
@@ -2614,19 +2677,42 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
             a.sfhi = a.sub + slots;
         }
         a.lane_of = dd ? p->d_rlane : p->d_lane;
-        // kernel-time bracket (kg_profile_read): the launch carries the pair itself (LaunchSelect.ev_start / ev_stop),
-        // nothing is recorded on the stream around a kernel of some 18 us. The pair goes on ev_live only
-        // once the launch took it; every failure hands it back to the pool
-        st = bracket_take(ctx, &a.ev_start, &a.ev_stop);
+        // kernel-time bracket (kg_profile_read). One launch: the kernel times itself with the device clock (a.prof; the
+        // begin word lies in the batch's accumulator buffer, so sacc_dirty clears it too), the launch is the plain one
+        // and the host only counts it, once it succeeded. Two launches, a device without a wall clock
+        // rate, or KG_PROFILE_BOUND_EVENTS (read per call: the tool and the tests compare both brackets): the launch
+        // carries a pooled event pair itself (LaunchSelect.ev_start / ev_stop), nothing is recorded on the stream. The
+        // pair goes on ev_live only once the launch took it; every failure hands it back to the pool
+        const uint32_t nc = a.range[0].n_chunks + a.range[1].n_chunks;
+        const char* phases = small_phases_file(a, lp);
+        st = KG_OK;
+        if (phases) {  // a launch of the measurement aid has no bracket: its tick pair is the scratch one in d_phases
+            if (ctx->phases_cap < (size_t)nc * 4 + 2) {
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                if (ctx->d_phases) hipFree(ctx->d_phases);
+                ctx->d_phases = nullptr;
+                ctx->phases_cap = 0;
+                HIP_TRY(ctx, hipMalloc(&ctx->d_phases, sizeof(uint64_t) * ((size_t)nc * 4 + 2)));
+                ctx->phases_cap = (size_t)nc * 4 + 2;
+            }
+            a.phases = true;
+            a.prof = ctx->d_phases;
+        } else if (ctx->profiling && a.small_replicas && !std::getenv("KG_PROFILE_BOUND_EVENTS")) {
+            st = ensure_prof(ctx, &a.prof);
+        }
+        if (st == KG_OK && !a.prof) st = bracket_take(ctx, &a.ev_start, &a.ev_stop);
         if (st == KG_OK) {
             const hipError_t le = launch_select(a, ctx->stream);
             if (le != hipSuccess) {
                 bracket_drop(ctx, a.ev_start, a.ev_stop);
                 st = fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR, "launch_select(a, ctx->stream): %s",
                           hipGetErrorString(le));
+            } else if (a.prof && !phases) {
+                ctx->prof_pending++;
             } else if (a.ev_start) {
                 ctx->ev_live.emplace_back(a.ev_start, a.ev_stop);
             }
+            if (st == KG_OK && phases) st = small_phases_write(ctx, phases, nc);
         }
         // a failed call may have left a launch half done: the accumulators are zeroed again before the next one
         if (st != KG_OK && a.small_replicas) p->sacc_dirty = true;
@@ -4102,6 +4188,21 @@ kg_status kg_profile_read(kg_ctx* ctx, double* total_ms, uint64_t* launches, int
         ctx->ev_free.push_back(e);
     }
     ctx->ev_live.clear();
+    // the one-launch small selects that timed themselves: the device's tick sum and launch count since the last read
+    if (ctx->prof_pending) {
+        uint64_t h[2] = {0, 0};
+        HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_prof, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const uint64_t ticks = h[0] - ctx->prof_seen[0], n = h[1] - ctx->prof_seen[1], want = ctx->prof_pending;
+        ctx->prof_seen[0] = h[0];
+        ctx->prof_seen[1] = h[1];
+        ctx->prof_pending = 0;
+        if (n != want)
+            return fail(ctx, KG_DEVICE_ERROR, "device-timed selects: the device counted %llu launches, the host %llu",
+                        (unsigned long long)n, (unsigned long long)want);
+        ctx->prof_ms += (double)ticks / (double)ctx->clock_khz;
+        ctx->prof_launches += n;
+    }
     if (total_ms) *total_ms = ctx->prof_ms;
     if (launches) *launches = ctx->prof_launches;
     if (reset) {

@@ -20,6 +20,11 @@ workgroups share an address; "two": KG_NO_SMALL_FUSED_FINISH=1, the two launches
 replica rule is set from.
 --profile: the timed loop runs with the profile bracket on, as bench.py's does; every line also carries the host time of
 the submission loop alone (submit_ms_small: per call, before the final sync) and the bracket's device time per select.
+--bracket clock|events (with --profile): the one-launch select times itself with the device clock (the default) or
+keeps the event pair bound to its launch (KG_PROFILE_BOUND_EVENTS=1); every line says which bracket it used.
+--phases: where the one-launch kernel's time goes (KG_SMALL_PHASES: the kernel's instantiation that stores four clock
+readings per workgroup; config 2's shape only). One JSON line per snapshot: medians over workgroups and steps of the
+time from the launch's earliest entry to each workgroup's entry, loops done and ticket drawn, and to the finisher's end.
 --shares "0,0.02,...": synth.mixed()'s nodes thinned to these F_BIG shares (every other node kept, the first F_BIG
 nodes up to the share), for the break-even of the F_BIG gate in select_small. KG_SMALL_ALLOW_BIG=1 (set here) lifts
 that gate so that both paths can be timed above it.
@@ -50,7 +55,14 @@ def main():
     ap.add_argument("--chunks", default=None, help="KG_SMALL_CHUNKS for the new path's side of the A/B")
     ap.add_argument("--profile", action="store_true",
                     help="time with the profile bracket on (ctx.profile, as bench.py does) and report the bracket")
+    ap.add_argument("--bracket", choices=["clock", "events"], default="clock",
+                    help="with --profile: the one-launch select's bracket (device clock inside the launch / bound event pair)")
+    ap.add_argument("--phases", action="store_true", help="per-workgroup phase times of the one-launch kernel")
     a = ap.parse_args()
+    if a.bracket == "events":
+        os.environ["KG_PROFILE_BOUND_EVENTS"] = "1"
+    else:
+        os.environ.pop("KG_PROFILE_BOUND_EVENTS", None)
 
     import numpy as np
 
@@ -89,6 +101,41 @@ def main():
             ctx.profile(False)
             last["bracket_ms"] = ms / n if n else None
         return (t2 - t0) / a.steps * 1e3
+
+    def phases_of(snap):
+        """Median microseconds (100 MHz device clock) over a.steps launches, each read from the KG_SMALL_PHASES file."""
+        import tempfile
+        fd, path = tempfile.mkstemp(suffix=".phases")
+        os.close(fd)
+        for _ in range(a.warmup):
+            engine.eval_select_async(snap, batch, 1)
+        ctx.sync()
+        os.environ["KG_SMALL_PHASES"] = path
+        try:
+            for _ in range(a.steps):
+                engine.eval_select_async(snap, batch, 1)
+            ctx.sync()
+        finally:
+            del os.environ["KG_SMALL_PHASES"]
+        raw = np.fromfile(path, dtype=np.uint64)
+        os.remove(path)
+        per, at = [], 0
+        while at < len(raw):
+            nc = int(raw[at])
+            t = raw[at + 1:at + 1 + 4 * nc].reshape(nc, 4).astype(np.int64)
+            at += 1 + 4 * nc
+            t0 = t[:, 0].min()
+            fin = t[t[:, 3] != 0]
+            assert len(fin) == 1, "one finisher per launch"
+            per.append(dict(workgroups=nc, entry=np.median(t[:, 0] - t0), entry_max=(t[:, 0] - t0).max(),
+                            loops=np.median(t[:, 1] - t0), loops_max=(t[:, 1] - t0).max(),
+                            ticket=np.median(t[:, 2] - t0), ticket_max=(t[:, 2] - t0).max(),
+                            loops_own=np.median(t[:, 1] - t[:, 0]), ticket_own=np.median(t[:, 2] - t[:, 1]),
+                            finisher_ticket=fin[0, 2] - t0, finisher_end=fin[0, 3] - t0, finisher_own=fin[0, 3] - fin[0, 2]))
+        if not per:
+            return None
+        return {k + ("_us" if k != "workgroups" else ""): float(np.median([q[k] for q in per])) / (1.0 if k == "workgroups" else 100.0)
+                for k in per[0]} | {"launches": len(per)}
 
     def with_env(name, value, fn):
         os.environ[name] = value
@@ -130,12 +177,18 @@ def main():
                 return with_env("KG_NO_SMALL_FUSED_FINISH", "1", lambda: time_select(snap))
             return with_env("KG_SMALL_REPLICAS", "4096" if r == "all" else r, lambda: time_select(snap))
 
+        if a.phases:
+            print(json.dumps(dict(head, phases=phases_of(snap), unit="us from the launch's earliest workgroup entry, medians "
+                                  "over workgroups, then over launches (*_own: within the workgroup)")), flush=True)
+            snap.close()
+            continue
         for rep in range(a.repeat):
             if a.replicas:
                 for r in a.replicas.split(","):
                     ms = with_env("KG_SMALL_CHUNKS", a.chunks, lambda: time_replicas(r)) if a.chunks else time_replicas(r)
                     print(json.dumps(dict(head, repeat=rep, chunks=a.chunks, replicas=r, select_ms_small=ms,
-                                          profile=a.profile, submit_ms_small=last["submit_ms"],
+                                          profile=a.profile, bracket=a.bracket if a.profile and r != "two" else
+                                          "events" if a.profile else None, submit_ms_small=last["submit_ms"],
                                           bracket_ms_small=last["bracket_ms"])), flush=True)
             elif a.sweep:
                 for setting in a.sweep.split(";"):
@@ -143,7 +196,7 @@ def main():
                     print(json.dumps(dict(head, repeat=rep, chunks=setting, select_ms_small=ms)), flush=True)
             else:
                 small = with_env("KG_SMALL_CHUNKS", a.chunks, lambda: time_select(snap)) if a.chunks else time_select(snap)
-                host = dict(profile=a.profile, submit_ms_small=last["submit_ms"], bracket_ms_small=last["bracket_ms"])
+                host = dict(profile=a.profile, bracket=a.bracket if a.profile else None, submit_ms_small=last["submit_ms"], bracket_ms_small=last["bracket_ms"])
                 two = with_env("KG_NO_SMALL_FUSED_FINISH", "1", lambda: time_select(snap))
                 general = with_env("KG_NO_SMALL_SELECT", "1", lambda: time_select(snap))
                 print(json.dumps(dict(head, repeat=rep, chunks=a.chunks, select_ms_small=small, select_ms_two_launch=two,
