@@ -147,6 +147,10 @@ typedef enum kg_status {
 #define KG_ST_NUMA_INSUF_CPU 0x1000u  /* "Insufficient NUMA cpu"                              */
 #define KG_ST_NUMA_INSUF_MEM 0x2000u  /* "Insufficient NUMA memory"                           */
 #define KG_ST_NUMA_INSUF_NODE 0x4000u /* "node(s) Insufficient NUMA Node resources" (no zones)  */
+/* The node is outside the pod's candidate node set (kg_pods_set_node_sets): a Filter of the host's that ran before
+ * every koord plugin (nodeSelector / affinity, taints, spec.nodeName, PodTopologySpread, a PreFilterResult) and after
+ * the ElasticQuota PreFilter gate. Outside every *_MASK. */
+#define KG_ST_NODE_EXCLUDED 0x8000u
 #define KG_ST_NUMA_AMP_CPU 0x10000u  /* ErrInsufficientAmplifiedCPU                          */
 #define KG_ST_NUMA_CONFLICT 0x20000u /* ErrNotMatchNUMATopology (UnschedulableAndUnresolvable) */
 #define KG_ST_NUMA_NO_RES 0x40000u   /* "node(s) missing NUMA resources"                      */
@@ -592,6 +596,36 @@ kg_status kg_pods_upload(kg_pods* pods, const kg_pod_columns* cols, uint32_t n_p
  * 64-lane waves (the duplicates' keys and status are copied from their representative on the device; results are the
  * same). fast_lanes: the leading lanes on the float64 fast path. Either pointer may be NULL. Diagnostics only. */
 kg_status kg_pods_select_lanes(const kg_pods* pods, uint32_t* lanes, uint32_t* fast_lanes);
+/* Per-pod candidate node sets: the nodes each pod of the uploaded batch may use, as the scheduler narrowed them before
+ * koord's plugins run (nodeSelector and required node affinity, taints and tolerations, spec.nodeName,
+ * NodeUnschedulable, PodTopologySpread, a nominated node, a PreFilterResult). A pair (pod j, node i) with i outside j's
+ * set fails a Filter that runs before every koord plugin and after the ElasticQuota PreFilter gate:
+ *   kg_eval_select    (plain snapshots, k = 1..4) keys are the top-k over the candidate nodes only, an empty set gives
+ *                     keys 0, and kg_result_status flags a pod only for a candidate pair (a set lane is flagged when
+ *                     any candidate pair needs the host path);
+ *   kg_eval_verify    an excluded pair's status is its usual word | KG_ST_NODE_EXCLUDED and its total is -1; the score
+ *                     columns and numa_zone stay as they are without sets;
+ *   kg_eval_diagnose  flags 0: slot 15 counts the excluded nodes (the counted word is verify's); KG_DIAG_FIRST_PLUGIN:
+ *                     an excluded node's counted word is KG_ST_NODE_EXCLUDED alone (after KG_ST_QUOTA, before
+ *                     KG_ST_NRF_MASK); KG_DIAG_FEASIBLE counts candidate nodes only;
+ *   kg_replay         (plain snapshots) each pod's cycle picks among its candidates; out_reason carries
+ *                     KG_ST_NODE_EXCLUDED when the pod has an excluded node; the batch runs one pod per launch.
+ * Called after kg_pods_upload; everything is copied. A later kg_pods_upload clears the sets, sets == NULL clears them
+ * too. Bits at or above n_nodes in a set's last word are ignored. KG_INVALID_ARG: no batch uploaded, a pod_set value
+ * outside [-1, n_sets), n_sets > 0 with bits == NULL. An evaluating call returns KG_INVALID_ARG when its snapshot's
+ * node count differs from n_nodes.
+ * KG_UNSUPPORTED while the batch carries sets: every evaluating call on a snapshot with config-5 tables
+ * (KG_PLUGIN_EXT: the per-pod NormalizeScore runs over the narrowed set) and kg_shard_select (the exchange of the
+ * shards). kg_batch_schedule, kg_reserve, kg_assume*, kg_forget* and kg_unreserve name their node themselves and do
+ * not read the sets. The symbol is new within ABI 14: a binding resolves it at load time. */
+typedef struct kg_node_sets {
+    const int32_t* pod_set;  /* [n_pods of the uploaded batch]; -1 = every node (no set) */
+    const uint32_t* bits;    /* [n_sets][(n_nodes + 31) / 32]: bit (i & 31) of word (i >> 5) set = the node at snapshot
+                                position i is a candidate. The position is the row of the node upload; index_base is
+                                not added */
+    uint32_t n_sets, n_nodes;
+} kg_node_sets;
+kg_status kg_pods_set_node_sets(kg_pods* pods, const kg_node_sets* sets /* NULL clears */);
 kg_status kg_pods_destroy(kg_pods* pods);
 
 /* Full per-plugin Filter/Score matrix for every (pod, node) pair (the FilterPlugin/ScorePlugin
@@ -622,7 +656,8 @@ kg_status kg_result_status(kg_pods* pods, uint32_t* out_status);
  *            stays 0); slot KG_DIAG_FEASIBLE: nodes whose counted word is 0; slots 49..63 are written as 0.
  *   flags    0: the counted word is the pair's status word as kg_eval_verify reports it (every failing plugin's
  *            bits). KG_DIAG_FIRST_PLUGIN: that word masked to its first non-empty group in the framework's order,
- *            which stops at a node's first failing plugin: the ElasticQuota PreFilter gate (KG_ST_QUOTA), then the
+ *            which stops at a node's first failing plugin: the ElasticQuota PreFilter gate (KG_ST_QUOTA),
+ *            KG_ST_NODE_EXCLUDED (a batch with candidate node sets: the host's Filters ran before koord's), then the
  *            filter order of config/manager/scheduler-config.yaml:69-74: KG_ST_NRF_MASK, KG_ST_LA_MASK,
  *            KG_ST_NUMA_MASK | KG_ST_UNSUPPORTED, KG_ST_DEV_MASK | KG_ST_DEV_RSV, KG_ST_RSV_MASK. The DeviceShare
  *            code slots and KG_DIAG_FEASIBLE follow the counted word.

@@ -73,6 +73,7 @@ KG_ST_NUMA_INSUF_CPU = 0x1000   # BestEffort Reserve: "Insufficient NUMA cpu"
 KG_ST_NUMA_INSUF_MEM = 0x2000   # "Insufficient NUMA memory"
 KG_ST_NUMA_INSUF_NODE = 0x4000  # "node(s) Insufficient NUMA Node resources"
 KG_ST_NUMA_RESERVE = KG_ST_NUMA_INSUF_CPU | KG_ST_NUMA_INSUF_MEM | KG_ST_NUMA_INSUF_NODE
+KG_ST_NODE_EXCLUDED = 0x8000    # the node is outside the pod's candidate node set (kg_pods_set_node_sets)
 ZONE_RESERVE_FAIL = 0x20        # numa_zone code | (KG_ST_NUMA_INSUF_* >> 12): the pair's Reserve fails
 KG_ST_NUMA_AMP_CPU = 0x10000
 KG_ST_NUMA_CONFLICT = 0x20000
@@ -142,6 +143,14 @@ KG_BATCH_ASSUMED, KG_BATCH_FAILED, KG_BATCH_SIBLING, KG_BATCH_ROLLED_BACK, KG_BA
 
 _p64 = C.POINTER(C.c_int64)
 _pu32 = C.POINTER(C.c_uint32)
+
+
+class KgNodeSets(C.Structure):
+    """kg_node_sets: per-pod candidate node sets (koordinator_amd.nodesets builds the arrays)."""
+    _fields_ = [("pod_set", C.POINTER(C.c_int32)), ("bits", C.POINTER(C.c_uint32)), ("n_sets", C.c_uint32),
+                ("n_nodes", C.c_uint32)]
+
+
 _pf64 = C.POINTER(C.c_double)
 _pi32 = C.POINTER(C.c_int32)
 

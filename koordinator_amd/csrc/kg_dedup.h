@@ -10,7 +10,10 @@
 //   the flags word as built            KG_POD_* bits (low 16), the pod's NUMA policy (<< 16), POD_FASTV
 // (pmap is null on the plain path; the config-5 columns are read by the ext kernels only, and batches that carry them
 // are not deduplicated.)
+// A batch with candidate node sets (kg_pods_set_node_sets) adds the pod's set id to the row: two pods share a
+// representative only when they also name the same set (-1: none).
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -22,10 +25,12 @@ constexpr int DEDUP_COLS = 9;
 struct DedupRows {
     const int64_t* col[DEDUP_COLS];  // each [n]
     const uint32_t* flags;           // [n]
+    const int32_t* set;              // [n] candidate node set of the pod, -1 = none; nullptr: the batch carries no sets
 };
 
 inline bool dedup_row_equal(const DedupRows& r, uint32_t a, uint32_t b) {
     if (r.flags[a] != r.flags[b]) return false;
+    if (r.set && r.set[a] != r.set[b]) return false;
     for (int c = 0; c < DEDUP_COLS; c++)
         if (r.col[c][a] != r.col[c][b]) return false;
     return true;
@@ -34,6 +39,7 @@ inline bool dedup_row_equal(const DedupRows& r, uint32_t a, uint32_t b) {
 struct DedupHash {
     uint64_t operator()(const DedupRows& r, uint32_t j) const {
         uint64_t h = 0x9E3779B97F4A7C15ull ^ r.flags[j];
+        if (r.set) h ^= (uint64_t)(uint32_t)r.set[j] << 32;
         for (int c = 0; c < DEDUP_COLS; c++) {
             h ^= (uint64_t)r.col[c][j];
             h *= 0xFF51AFD7ED558CCDull;
@@ -86,6 +92,32 @@ inline void dedup_order(const uint32_t* order, uint32_t n, uint32_t n_fast, cons
     }
     *n_rep_fast = mf;
     *n_rep = m;
+}
+
+// Split a lane list (order or rorder: the first n_fast entries fast lanes grouped by wave kind, then the integer lanes)
+// of a batch with candidate node sets. Lanes without a set stay in `list`, in their order (plain_fast of them fast):
+// the general-path kernels serve them unchanged, over a shorter list. Lanes with a set go to set_list, sorted by (set
+// id, fast or integer lane, wave kind) so that a wave's lanes mostly share one set and one loop; kind[row] = the row's
+// wave kind (0..2 fast kinds, 3 = integer lane). Returns the number of set lanes.
+inline uint32_t dedup_split_sets(uint32_t* list, uint32_t n, uint32_t n_fast, const int32_t* set, const uint8_t* kind,
+                                 uint32_t* set_list, uint32_t* plain, uint32_t* plain_fast) {
+    uint32_t m = 0, mf = 0, ns = 0;
+    for (uint32_t t = 0; t < n; t++) {
+        const uint32_t j = list[t];
+        if (set[j] >= 0) {
+            set_list[ns++] = j;
+        } else {
+            list[m++] = j;
+            if (t < n_fast) mf = m;
+        }
+    }
+    std::stable_sort(set_list, set_list + ns, [&](uint32_t a, uint32_t b) {
+        if (set[a] != set[b]) return set[a] < set[b];
+        return kind[a] < kind[b];  // the integer kind sorts last: fast lanes, then integer lanes
+    });
+    *plain = m;
+    *plain_fast = mf;
+    return ns;
 }
 
 // 64-lane waves of a select over n_lanes lanes whose first n_fast are fast lanes (the two groups launch separately)

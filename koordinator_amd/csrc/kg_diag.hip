@@ -76,12 +76,19 @@ __device__ __forceinline__ void diag_flush(const DiagAcc& a, uint32_t* __restric
 
 // Records [begin + chunk * y, ...) of [begin, end) for the rows of block x; counts[t][KG_DIAG_SLOTS] zeroed by the
 // launcher. chunk <= DIAG_MAX_CHUNK.
-template <bool EXACT, bool EXT>
+// SETS (plain plugin set only): the batch carries candidate node sets. The lane keeps its set's 64-bit word of the
+// record-order table for the 64-record block it walks (reloaded when the wave-uniform record index crosses a block;
+// a pod without a set: all ones). A record outside the set adds KG_ST_NODE_EXCLUDED to the counted word or, with
+// first_plugin, is counted under that bit alone: the host's Filter ran before every koord plugin (there is no
+// ElasticQuota gate on the plain path). Without SETS the three arguments are not read.
+template <bool EXACT, bool EXT, bool SETS = false>
 __global__ __launch_bounds__(256) void k_diagnose(const NodeRec* __restrict__ nodes, const ZoneRec* __restrict__ zones,
                                                   ExtDev e, PodsDev pods, const uint32_t* __restrict__ rows,
                                                   uint32_t n_rows, uint32_t begin, uint32_t end, uint32_t chunk, KCfg cfg,
                                                   const uint32_t* __restrict__ qst, uint32_t first_plugin,
-                                                  uint32_t* __restrict__ counts) {
+                                                  uint32_t* __restrict__ counts, const int32_t* __restrict__ pod_set,
+                                                  const uint64_t* __restrict__ tab, uint32_t words) {
+    static_assert(!(EXT && SETS), "candidate node sets are not served on config-5 snapshots");
     const GridBlock b = xcd_block();  // whole record chunks per XCD (kg_eval.h)
     const uint32_t t = b.x * blockDim.x + threadIdx.x;
     if ((t & ~63u) >= n_rows) return;  // uniform: a wave past the last row (no barrier below)
@@ -99,6 +106,18 @@ __global__ __launch_bounds__(256) void k_diagnose(const NodeRec* __restrict__ no
         for (uint32_t rec = lo; rec < hi; rec++) {
             uint32_t w = eval_pair_ext<EXACT>(cfg, e, nodes[rec].v, zones + rec, dev_of(e, rec), rec, p, px, q).status;
             if (first_plugin) w = diag_first_plugin(w);
+            diag_count(a, w, diag_derived(w));
+        }
+    } else if constexpr (SETS) {
+        const int32_t set = pod_set[j];
+        const uint64_t* srow = tab + (size_t)(set < 0 ? 0 : set) * words;
+        uint64_t word = ~0ull;
+        for (uint32_t rec = lo; rec < hi; rec++) {
+            if (set >= 0 && (rec == lo || (rec & 63u) == 0u)) word = srow[rec >> 6];
+            uint32_t w = eval_pair<EXACT, false, true, false, false>(cfg, nodes[rec].v, zones + rec, p).status;
+            const bool excl = !((word >> (rec & 63u)) & 1ull);
+            if (first_plugin) w = excl ? (uint32_t)KG_ST_NODE_EXCLUDED : diag_first_plugin(w);
+            else w |= excl ? (uint32_t)KG_ST_NODE_EXCLUDED : 0u;
             diag_count(a, w, diag_derived(w));
         }
     } else {
@@ -121,8 +140,10 @@ static uint32_t diag_target_blocks() {
 
 hipError_t launch_diagnose(const NodeRec* nodes, const ZoneRec* zones, const ExtDev& e, bool ext, const PodsDev& pods,
                            const uint32_t* rows, uint32_t n_rows, uint32_t n_nodes, const KCfg& cfg, bool exact,
-                           const uint32_t* qst, bool first_plugin, uint32_t* counts, hipStream_t s) {
+                           const uint32_t* qst, bool first_plugin, uint32_t* counts, hipStream_t s,
+                           const int32_t* pod_set, const uint64_t* tab, uint32_t words) {
     if (n_rows == 0 || n_nodes == 0) return hipSuccess;
+    if (pod_set && (ext || !tab || words != (n_nodes + 63) / 64)) return hipErrorInvalidValue;
     // whole waves of rows, up to four per workgroup: a short row list leaves no idle wave walking records
     const uint32_t block = std::min<uint32_t>(256u, (n_rows + 63u) / 64u * 64u);
     const uint32_t chunk = diag_chunk(n_nodes, n_rows, block, diag_target_blocks());
@@ -131,10 +152,14 @@ hipError_t launch_diagnose(const NodeRec* nodes, const ZoneRec* zones, const Ext
     for (uint64_t begin = 0; begin < n_nodes; begin += (uint64_t)MAX_Y * chunk) {
         const uint32_t end = (uint32_t)std::min<uint64_t>(n_nodes, begin + (uint64_t)MAX_Y * chunk);
         const dim3 grid(gx, (end - (uint32_t)begin + chunk - 1) / chunk);
-#define KG_DIAG_LAUNCH(EXACT, EXT)                                                                                     \
-    k_diagnose<EXACT, EXT><<<grid, block, 0, s>>>(nodes, zones, e, pods, rows, n_rows, (uint32_t)begin, end, chunk, cfg, \
-                                                  qst, first_plugin ? 1u : 0u, counts)
-        if (ext) {
+#define KG_DIAG_LAUNCH(EXACT, EXT, ...)                                                                              \
+    k_diagnose<EXACT, EXT, ##__VA_ARGS__><<<grid, block, 0, s>>>(nodes, zones, e, pods, rows, n_rows, (uint32_t)begin, \
+                                                                 end, chunk, cfg, qst, first_plugin ? 1u : 0u, counts, \
+                                                                 pod_set, tab, words)
+        if (pod_set) {
+            if (exact) KG_DIAG_LAUNCH(true, false, true);
+            else KG_DIAG_LAUNCH(false, false, true);
+        } else if (ext) {
             if (exact) KG_DIAG_LAUNCH(true, true);
             else KG_DIAG_LAUNCH(false, true);
         } else {

@@ -252,7 +252,8 @@ hipError_t launch_verify(const NodeRec* nodes, const ZoneRec* zones, const PodsD
                          uint32_t n_nodes, const KCfg& cfg, bool exact, const VerifyDev& o, hipStream_t s);
 hipError_t launch_replay_step(NodeRec* nodes, ZoneRec* zones, const PodsDev& pods, uint32_t n_pods, uint32_t n_nodes,
                               uint32_t index_base, const KCfg& cfg, bool exact, const uint32_t* step_base,
-                              uint32_t step_off, uint64_t* winners, int8_t* zsel, uint32_t* reason, hipStream_t s);
+                              uint32_t step_off, uint64_t* winners, int8_t* zsel, uint32_t* reason, hipStream_t s,
+                              const int32_t* pod_set = nullptr, const uint64_t* tab = nullptr, uint32_t words = 0);
 hipError_t launch_bump(uint32_t* step_base, uint32_t by, hipStream_t s);
 hipError_t launch_rb_window(const LaunchRb& a, hipStream_t s);
 hipError_t launch_assume(NodeRec* nodes, ZoneRec* zones, const PodsDev& pods, uint32_t pod, uint32_t node,

@@ -23,53 +23,9 @@
 
 #include "kg_eval.h"
 #include "kg_kernels.h"
+#include "kg_topk.h"
 
 namespace kg {
-
-template <int K>
-__device__ __forceinline__ void topk_insert(uint64_t (&top)[K], uint64_t key) {
-    if constexpr (K == 1) {
-        top[0] = key > top[0] ? key : top[0];
-    } else {
-        // a wave-uniform skip when no lane's key enters its top-K (most records once the lists have filled): the
-        // cascade below leaves top unchanged for a key not above top[K-1], so the lanes that do not insert may run it
-        if (!__any(key > top[K - 1])) return;
-#pragma unroll
-        for (int t = 0; t < K; t++) {
-            const uint64_t cur = top[t];
-            const bool gt = key > cur;
-            top[t] = gt ? key : cur;
-            key = gt ? cur : key;
-        }
-    }
-}
-
-// Insert a lane's top-K (descending, zeros = none) into the K shared slots of its pod, out[0..K), by an
-// atomicMax cascade: each key goes down the slots, an atomicMax at slot u keeps the larger of (slot, key) and
-// the smaller continues to slot u + 1. Whatever the interleaving of the lanes (chunks) that insert into one
-// pod, slot u ends as the u-th largest key inserted (the values passed below slot u are exactly its arrivals
-// minus their maximum), and slot u >= slot u + 1 at every instant; slots only grow. So a key that is not
-// above slot K-1 (read once, a lower bound of every slot from then on) can stop.
-template <int K>
-__device__ __forceinline__ void topk_atomic(uint64_t* out, const uint64_t (&top)[K]) {
-    if (top[0] == 0ull) return;
-    const uint64_t floor = __hip_atomic_load(out + (K - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int t = 0; t < K; t++) {
-        uint64_t carry = top[t];
-        if (carry <= floor) break;  // top is descending: every later key stops too
-#pragma unroll
-        for (int u = 0; u < K; u++) {
-            if (carry <= floor) break;
-            const uint64_t old = atomicMax((unsigned long long*)(out + u), (unsigned long long)carry);
-            carry = old < carry ? old : carry;
-        }
-    }
-}
-
-__device__ __forceinline__ uint32_t rec_gidx(const NodeRec& r, uint32_t index_base) {
-    return index_base + node_index(r);
-}
 
 // Records [begin, end) are walked in chunks of `chunk`; blockIdx.y = chunk, partial row = part0 + chunk.
 // FAST: pods and weights fit the float64 fast path (host check); records flagged F_BIG are skipped
@@ -811,12 +767,16 @@ __device__ __forceinline__ uint64_t wave_max_key(uint64_t k) {
 // One wave per workgroup (no LDS, no barrier): lane = node record. The zone each lane chose for its
 // node in the previous step is kept in zsel, so the winner's Reserve needs no re-evaluation; the
 // winner key and both pods are loaded up front, independently of each other.
-template <bool EXACT>
+// SETS: the batch carries candidate node sets (pod_set, and tab: the sets in record order, `words` 64-bit words each,
+// kg_sets.h). A workgroup is the 64 records of table word blockIdx.x: a record outside the pod's set keeps key 0 and
+// adds KG_ST_NODE_EXCLUDED to its status word. Without SETS the three arguments are not read.
+template <bool EXACT, bool SETS>
 __global__ __launch_bounds__(64) void k_replay(NodeRec* __restrict__ nodes, ZoneRec* __restrict__ zones, PodsDev pods,
                                                uint32_t n_pods, uint32_t n_nodes, uint32_t index_base, KCfg cfg,
                                                const uint32_t* __restrict__ step_base, uint32_t step_off,
                                                uint64_t* __restrict__ winners, int8_t* __restrict__ zsel,
-                                               uint32_t* __restrict__ reason) {
+                                               uint32_t* __restrict__ reason, const int32_t* __restrict__ pod_set,
+                                               const uint64_t* __restrict__ tab, uint32_t words) {
     const uint32_t step = (step_base ? *step_base : 0u) + step_off;
     if (step > n_pods) return;  // uniform: past the end of the batch
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
@@ -845,6 +805,13 @@ __global__ __launch_bounds__(64) void k_replay(NodeRec* __restrict__ nodes, Zone
         key = pair_key(cfg, o, rec_gidx(nodes[i], index_base));
         zsel[i] = (int8_t)o.zone;
         st = o.status;
+        if constexpr (SETS) {
+            const int32_t set = pod_set[step];  // uniform
+            if (set >= 0 && !((tab[(size_t)set * words + blockIdx.x] >> threadIdx.x) & 1ull)) {
+                key = 0;
+                st |= KG_ST_NODE_EXCLUDED;
+            }
+        }
     }
     key = wave_max_u64(key);
     if (threadIdx.x == 0 && key) atomicMax((unsigned long long*)&winners[step], (unsigned long long)key);
@@ -1661,14 +1628,21 @@ hipError_t launch_verify(const NodeRec* nodes, const ZoneRec* zones, const PodsD
 
 hipError_t launch_replay_step(NodeRec* nodes, ZoneRec* zones, const PodsDev& pods, uint32_t n_pods, uint32_t n_nodes,
                               uint32_t index_base, const KCfg& cfg, bool exact, const uint32_t* step_base,
-                              uint32_t step_off, uint64_t* winners, int8_t* zsel, uint32_t* reason, hipStream_t s) {
+                              uint32_t step_off, uint64_t* winners, int8_t* zsel, uint32_t* reason, hipStream_t s,
+                              const int32_t* pod_set, const uint64_t* tab, uint32_t words) {
     dim3 grid((n_nodes + 63) / 64), block(64);
-    if (exact)
-        k_replay<true><<<grid, block, 0, s>>>(nodes, zones, pods, n_pods, n_nodes, index_base, cfg, step_base,
-                                              step_off, winners, zsel, reason);
-    else
-        k_replay<false><<<grid, block, 0, s>>>(nodes, zones, pods, n_pods, n_nodes, index_base, cfg, step_base,
-                                               step_off, winners, zsel, reason);
+    if (pod_set && (!tab || words != (n_nodes + 63) / 64)) return hipErrorInvalidValue;
+#define KG_REPLAY(EXACTV, SETSV)                                                                                     \
+    k_replay<EXACTV, SETSV><<<grid, block, 0, s>>>(nodes, zones, pods, n_pods, n_nodes, index_base, cfg, step_base,  \
+                                                   step_off, winners, zsel, reason, pod_set, tab, words)
+    if (pod_set) {
+        if (exact) KG_REPLAY(true, true);
+        else KG_REPLAY(false, true);
+    } else {
+        if (exact) KG_REPLAY(true, false);
+        else KG_REPLAY(false, false);
+    }
+#undef KG_REPLAY
     return KG_LAUNCH_CHECK();
 }
 

@@ -15,6 +15,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -31,6 +32,7 @@
 #include "kg_diag.h"
 #include "kg_kernels.h"
 #include "kg_layout.h"
+#include "kg_sets.h"
 
 using namespace kg;
 
@@ -136,6 +138,10 @@ struct kg_snap {
     // Generation: bumped by every call that changes what the snapshot holds (upload, row update, Assume /
     // Forget, replay, quota / reservation upload); kg_snapshot_generation reads it.
     uint64_t gen = 0;
+    // Record layout: uid names this snapshot object among all the process has created, layout counts the placements of
+    // its records (place_records: an upload, a row update that moves a record to the other storage class). A batch's
+    // record-order table of candidate node sets is valid for one (uid, layout); gen does not serve: every Reserve bumps it.
+    uint64_t uid = 0, layout = 0;
     // batched row updates: staged records (NodeRec, ZoneRec[, DevRec] per row) and their positions
     uint8_t* d_stage = nullptr;
     uint32_t* d_stage_pos = nullptr;
@@ -302,6 +308,35 @@ struct kg_pods {
     hipGraphExec_t bexec = nullptr;
     std::vector<uint8_t> bkey;
     LaunchRb rb_args{};
+    // Candidate node sets (kg_pods_set_node_sets), cleared by every upload. sets_given: a descriptor is in force
+    // (n_nodes is checked by every evaluating call); any_set: some pod names a set, the lane lists are split: d_order /
+    // d_rorder hold the lanes without a set (n_plain_lanes / n_plain_fast of d_order, n_rep_plain / n_rep_plain_fast of
+    // d_rorder), d_sorder / d_srorder the pods / representatives with one, sorted by set (kg_dedup.h dedup_split_sets).
+    // n_rep / n_rep_fast count both kinds (the dedup gate and kg_pods_select_lanes).
+    bool batch_uploaded = false, sets_given = false, any_set = false;
+    std::vector<uint8_t> h_wk;        // per pod wave kind (0..2 fast kinds, 3 integer lane), kept by the upload
+    std::vector<int32_t> h_pod_set;   // [n]
+    std::vector<uint32_t> h_set_bits; // [n_sets][words32], tail bits cleared
+    uint32_t set_n_sets = 0, set_n_nodes = 0;
+    uint32_t n_plain_lanes = 0, n_plain_fast = 0, n_rep_plain = 0, n_rep_plain_fast = 0, n_set_lanes = 0, n_rep_set = 0;
+    int32_t* d_pod_set = nullptr;     // [cap]
+    uint32_t* d_sorder = nullptr;     // [cap]
+    uint32_t* d_srorder = nullptr;    // [cap]
+    uint32_t* d_set_bits = nullptr;
+    uint64_t* d_set_tab = nullptr;    // [n_sets][words]: record order, for (tab_uid, tab_layout)
+    size_t set_bits_cap = 0, set_tab_cap = 0;  // words
+    bool tab_valid = false;
+    uint64_t tab_uid = 0, tab_layout = 0;
+    SetsDev sets_dev() const {
+        SetsDev d{};
+        d.pod_set = d_pod_set;
+        d.bits = d_set_bits;
+        d.tab = d_set_tab;
+        d.words32 = sets_words32(set_n_nodes);
+        d.words = sets_words(set_n_nodes);
+        d.n_sets = set_n_sets;
+        return d;
+    }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -771,6 +806,7 @@ void place_records(kg_snap* s, std::vector<NodeRec>& recs, std::vector<ZoneRec>&
         if (cpus) s->h_cpu_alloc[p] = (*cpus)[i];
     }
     s->n0 = n0;
+    s->layout++;
     count_topo(s);
 }
 
@@ -909,6 +945,8 @@ kg_status kg_snapshot_create(kg_ctx* ctx, const kg_config* cfg, uint32_t n_nodes
     if ((uint64_t)index_base + n_nodes > 0x7FFFFFFFull)
         return fail(ctx, KG_INVALID_ARG, "node index range exceeds 2^31");
     kg_snap* s = new kg_snap();
+    static std::atomic<uint64_t> next_uid{1};
+    s->uid = next_uid.fetch_add(1, std::memory_order_relaxed);
     s->ctx = ctx;
     s->cfg = *cfg;
     kg_status st = build_kcfg(ctx, cfg, &s->kcfg);
@@ -1701,7 +1739,174 @@ kg_status kg_pods_upload(kg_pods* p, const kg_pod_columns* cols, uint32_t n) {
     p->n_x = nx;
     p->n_dclass = (uint32_t)classes.size();
     p->dev_unclassed = unclassed;
+    // a new batch carries no candidate node sets; the wave kinds stay for kg_pods_set_node_sets' lane lists
+    p->batch_uploaded = true;
+    p->sets_given = p->any_set = p->tab_valid = false;
+    p->h_wk.assign(wk.begin(), wk.begin() + n);
+    p->n_plain_lanes = n;
+    p->n_plain_fast = n_fast;
+    p->n_rep_plain = n_rep;
+    p->n_rep_plain_fast = n_rep_fast;
+    p->n_set_lanes = p->n_rep_set = 0;
     return KG_OK;
+}
+
+// Lane lists, rep and the row-to-lane tables of the uploaded batch from its staged rows (still in p->h_in), with the
+// pods' set ids counted as part of the row; set == nullptr: no sets, exactly the lists kg_pods_upload built.
+static kg_status derive_lanes(kg_pods* p, const int32_t* set) {
+    kg_ctx* ctx = p->ctx;
+    const uint32_t n = p->n, n_fast = p->n_fast;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // as kg_pods_upload: nothing reads d_in on a side stream, the staging's last copy has completed
+    if (ctx->side) HIP_TRY(ctx, hipStreamSynchronize(ctx->side));
+    if (ctx->side2) HIP_TRY(ctx, hipStreamSynchronize(ctx->side2));
+    if (p->in_pending) {
+        HIP_TRY(ctx, hipEventSynchronize(p->in_copied));
+        p->in_pending = false;
+    }
+    bool any = false;
+    for (uint32_t j = 0; set && j < n; j++) any |= set[j] >= 0;
+    if (any && !p->d_sorder) {
+        HIP_TRY(ctx, hipMalloc(&p->d_sorder, sizeof(uint32_t) * p->cap));
+        HIP_TRY(ctx, hipMalloc(&p->d_srorder, sizeof(uint32_t) * p->cap));
+    }
+    const PodLayout L = pod_layout(n);
+    uint8_t* h = p->h_in;
+    const uint8_t* wk = p->h_wk.data();
+    uint32_t* order = reinterpret_cast<uint32_t*>(h + L.order);
+    {
+        uint32_t cnt[4] = {0, 0, 0, 0};
+        for (uint32_t j = 0; j < n; j++) cnt[wk[j]]++;
+        uint32_t at[4] = {0, cnt[0], cnt[0] + cnt[1], cnt[0] + cnt[1] + cnt[2]};
+        for (uint32_t j = 0; j < n; j++) order[at[wk[j]]++] = j;
+    }
+    uint32_t* rp = reinterpret_cast<uint32_t*>(h + L.rep);
+    uint32_t* rorder = reinterpret_cast<uint32_t*>(h + L.rorder);
+    uint32_t n_rep = n, n_rep_fast = n_fast;
+    if (p->dedup) {
+        DedupRows rows{};
+        const int64_t* hc = reinterpret_cast<const int64_t*>(h + L.cols);
+        for (int c = 0; c < DEDUP_COLS; c++) rows.col[c] = hc + (size_t)c * n;
+        rows.flags = reinterpret_cast<const uint32_t*>(h + L.flags);
+        rows.set = any ? set : nullptr;
+        dedup_rows(rows, n, rp, p->dedup_slots);
+        dedup_order(order, n, n_fast, rp, rorder, &n_rep_fast, &n_rep);
+    }
+    uint32_t plain = n, plain_fast = n_fast, rplain = n_rep, rplain_fast = n_rep_fast, ns = 0, nrs = 0;
+    std::vector<uint32_t> sorder, srorder;
+    if (any) {
+        sorder.resize(n);
+        ns = dedup_split_sets(order, n, n_fast, set, wk, sorder.data(), &plain, &plain_fast);
+        if (p->dedup) {
+            srorder.resize(n_rep);
+            nrs = dedup_split_sets(rorder, n_rep, n_rep_fast, set, wk, srorder.data(), &rplain, &rplain_fast);
+        }
+    } else {
+        // row -> lane for the one-pod-block select (a batch with sets does not take it)
+        if (n <= 256)
+            for (uint32_t t = 0; t < n; t++) h[L.lane + order[t]] = (uint8_t)t;
+        if (p->dedup && n_rep <= 256) {
+            uint8_t* rl = h + L.rlane;
+            for (uint32_t t = 0; t < n_rep; t++) rl[rorder[t]] = (uint8_t)t;
+            for (uint32_t j = 0; j < n; j++)
+                if (rp[j] != j) rl[j] = rl[rp[j]];
+        }
+    }
+    if (n) {
+        // order, (pmap: unchanged,) rep, rorder, lane, rlane lie back to back in front of the config-5 regions
+        HIP_TRY(ctx, hipMemcpyAsync(p->d_in + L.order, h + L.order, L.ext - L.order, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(p->in_copied, ctx->stream));
+        p->in_pending = true;
+        if (ns) HIP_TRY(ctx, hipMemcpyAsync(p->d_sorder, sorder.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice, ctx->stream));
+        if (nrs) HIP_TRY(ctx, hipMemcpyAsync(p->d_srorder, srorder.data(), sizeof(uint32_t) * nrs, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the set lists are staged in pageable memory
+    }
+    p->any_set = any;
+    p->n_rep = n_rep;
+    p->n_rep_fast = n_rep_fast;
+    p->n_plain_lanes = plain;
+    p->n_plain_fast = plain_fast;
+    p->n_rep_plain = rplain;
+    p->n_rep_plain_fast = rplain_fast;
+    p->n_set_lanes = ns;
+    p->n_rep_set = nrs;
+    return KG_OK;
+}
+
+kg_status kg_pods_set_node_sets(kg_pods* p, const kg_node_sets* sets) {
+    if (!p) return KG_INVALID_ARG;
+    kg_ctx* ctx = p->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!p->batch_uploaded) return fail(ctx, KG_INVALID_ARG, "candidate node sets before kg_pods_upload");
+    if (!sets) {
+        const bool had = p->any_set;
+        p->sets_given = p->tab_valid = false;
+        p->h_pod_set.clear();
+        return had ? derive_lanes(p, nullptr) : KG_OK;
+    }
+    const uint32_t n = p->n, w32 = sets_words32(sets->n_nodes);
+    if (n && !sets->pod_set) return fail(ctx, KG_INVALID_ARG, "null pod_set");
+    if (sets->n_sets && !sets->bits) return fail(ctx, KG_INVALID_ARG, "%u sets without bits", sets->n_sets);
+    if (sets->n_sets > 65535u) return fail(ctx, KG_INVALID_ARG, "%u sets > 65535", sets->n_sets);
+    for (uint32_t j = 0; j < n; j++)
+        if (sets->pod_set[j] < -1 || sets->pod_set[j] >= (int64_t)sets->n_sets)
+            return fail(ctx, KG_INVALID_ARG, "pod %u: set %d outside [-1, %u)", j, sets->pod_set[j], sets->n_sets);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // copies: the set ids, and the bitmaps with the bits at or above n_nodes cleared
+    std::vector<int32_t> ids(sets->pod_set, sets->pod_set + n);
+    std::vector<uint32_t> bits(sets->bits, sets->bits + (size_t)sets->n_sets * w32);
+    if (sets->n_nodes & 31u)
+        for (uint32_t t = 0; t < sets->n_sets; t++) bits[(size_t)t * w32 + w32 - 1] &= (1u << (sets->n_nodes & 31u)) - 1u;
+    const size_t tab_words = (size_t)sets->n_sets * sets_words(sets->n_nodes);
+    if (bits.size() > p->set_bits_cap || tab_words > p->set_tab_cap) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        hipFree(p->d_set_bits);
+        hipFree(p->d_set_tab);
+        p->d_set_bits = nullptr;
+        p->d_set_tab = nullptr;
+        p->set_bits_cap = p->set_tab_cap = 0;
+        p->tab_valid = false;
+        HIP_TRY(ctx, hipMalloc(&p->d_set_bits, sizeof(uint32_t) * std::max<size_t>(bits.size(), 1)));
+        HIP_TRY(ctx, hipMalloc(&p->d_set_tab, sizeof(uint64_t) * std::max<size_t>(tab_words, 1)));
+        p->set_bits_cap = bits.size();
+        p->set_tab_cap = tab_words;
+    }
+    if (!p->d_pod_set) HIP_TRY(ctx, hipMalloc(&p->d_pod_set, sizeof(int32_t) * p->cap));
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(p->d_pod_set, ids.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    if (!bits.empty())
+        HIP_TRY(ctx, hipMemcpyAsync(p->d_set_bits, bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice,
+                                    ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // staged in pageable memory
+    p->h_pod_set.swap(ids);
+    p->h_set_bits.swap(bits);
+    p->set_n_sets = sets->n_sets;
+    p->set_n_nodes = sets->n_nodes;
+    p->sets_given = true;
+    p->tab_valid = false;
+    return derive_lanes(p, p->h_pod_set.data());
+}
+
+// A batch with candidate node sets against snapshot s: the node counts agree and the record-order table is the one of
+// this snapshot's current layout (rebuilt after a kg_snapshot_upload, a row update that moved a record, or for another
+// snapshot). No-op for a batch without a descriptor.
+static kg_status ensure_sets(kg_snap* s, kg_pods* p) {
+    kg_ctx* ctx = s->ctx;
+    if (!p->sets_given) return KG_OK;
+    if (p->set_n_nodes != s->n)
+        return fail(ctx, KG_INVALID_ARG, "candidate node sets over %u nodes, snapshot of %u", p->set_n_nodes, s->n);
+    if (!p->any_set || (p->tab_valid && p->tab_uid == s->uid && p->tab_layout == s->layout)) return KG_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_sets_table(s->d_nodes, s->n, p->sets_dev(), p->d_set_tab, ctx->stream));
+    p->tab_valid = true;
+    p->tab_uid = s->uid;
+    p->tab_layout = s->layout;
+    return KG_OK;
+}
+
+// Evaluating calls that do not serve a batch with sets.
+static kg_status refuse_sets(kg_snap* s, kg_pods* p, const char* what) {
+    if (!p->any_set) return KG_OK;
+    return fail(s->ctx, KG_UNSUPPORTED, "%s with candidate node sets (kg_pods_set_node_sets)", what);
 }
 
 kg_status kg_pods_destroy(kg_pods* p) {
@@ -1710,7 +1915,8 @@ kg_status kg_pods_destroy(kg_pods* p) {
     hipStreamSynchronize(p->ctx->stream);
     if (p->ctx->side) hipStreamSynchronize(p->ctx->side);  // a plain-pod select may still read the batch there
     if (p->ctx->side2) hipStreamSynchronize(p->ctx->side2);  // and a class-1 lane of the config-5 kernels
-    for (void* b : {(void*)p->d_ipairs, (void*)p->d_ipair_count, (void*)p->d_sacc})
+    for (void* b : {(void*)p->d_ipairs, (void*)p->d_ipair_count, (void*)p->d_sacc, (void*)p->d_pod_set, (void*)p->d_sorder,
+                    (void*)p->d_srorder, (void*)p->d_set_bits, (void*)p->d_set_tab})
         hipFree(b);
     for (void* b : {(void*)p->d_in, (void*)p->d_keys, (void*)p->d_winners, (void*)p->d_step, (void*)p->d_partial,
                     (void*)p->d_gather, (void*)p->d_qst, (void*)p->d_dev_max, (void*)p->d_rsv_max, (void*)p->d_pref,
@@ -1794,7 +2000,12 @@ kg_status kg_eval_verify(kg_snap* s, kg_pods* p, kg_verify_out* out) {
     std::lock_guard<std::mutex> g(ctx->mu);
     st = check_views(s);
     if (st != KG_OK) return st;
-    if (s->ext()) return ext_verify(s, p, out);
+    if (s->ext()) {
+        st = refuse_sets(s, p, "verify on a snapshot with config-5 tables");
+        return st != KG_OK ? st : ext_verify(s, p, out);
+    }
+    st = ensure_sets(s, p);
+    if (st != KG_OK) return st;
     const size_t pairs = (size_t)p->n * s->n;
     if (pairs == 0) return KG_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1810,6 +2021,8 @@ kg_status kg_eval_verify(kg_snap* s, kg_pods* p, kg_verify_out* out) {
     d.status = (uint32_t*)(d.total + pairs);
     d.zone = (int8_t*)(d.status + pairs);
     hipError_t e = launch_verify(s->d_nodes, s->d_zones, p->dev, p->n, s->n, s->kcfg, force_exact(), d, ctx->stream);
+    // excluded pairs: the output matrix is in snapshot order, like the uploaded bitmap
+    if (e == hipSuccess && p->any_set) e = launch_sets_verify(p->sets_dev(), p->n, s->n, d.status, d.total, ctx->stream);
     if (e == hipSuccess) {
         struct {
             void* dst;
@@ -1862,9 +2075,13 @@ kg_status kg_eval_diagnose(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_
     st = check_views(s);
     if (st != KG_OK) return st;
     if (s->ext()) {
+        st = refuse_sets(s, p, "diagnosis on a snapshot with config-5 tables");
+        if (st != KG_OK) return st;
         st = check_ext(s);
         if (st != KG_OK) return st;
     }
+    st = ensure_sets(s, p);
+    if (st != KG_OK) return st;
     if (n_rows == 0) return KG_OK;
     const size_t words = (size_t)n_rows * KG_DIAG_SLOTS;
     if (s->n == 0) {
@@ -1882,7 +2099,7 @@ kg_status kg_eval_diagnose(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_
         HIP_TRY(ctx, launch_ext_gate(p->dev, p->n, e, s->cfg.plugins, p->d_qst, nullptr, ctx->stream));
     HIP_TRY(ctx, launch_diagnose(s->d_nodes, s->d_zones, e, s->ext(), p->dev, rows ? p->d_diag_rows : nullptr, n_rows, s->n,
                                  s->kcfg, force_exact(), p->d_qst, (flags & KG_DIAG_FIRST_PLUGIN) != 0, p->d_diag,
-                                 ctx->stream));
+                                 ctx->stream, p->any_set ? p->d_pod_set : nullptr, p->d_set_tab, sets_words(s->n)));
     HIP_TRY(ctx, hipMemcpyAsync(out_counts, p->d_diag, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return KG_OK;
@@ -2601,7 +2818,9 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     if (k == 0 || k > (uint32_t)KG_TOPK_MAX) return fail(ctx, KG_INVALID_ARG, "k=%u outside [1, %d]", k, KG_TOPK_MAX);
     const uint32_t kk = k == 1 ? 1 : KG_TOPK_MAX;
     if (s->ext()) {
-        kg_status st0 = check_ext(s);
+        kg_status st0 = refuse_sets(s, p, "select on a snapshot with config-5 tables");
+        if (st0 != KG_OK) return st0;
+        st0 = check_ext(s);
         if (st0 != KG_OK) return st0;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         p->k_last = k;
@@ -2642,6 +2861,10 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         return record_end(ctx, e0, e1);
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    {
+        const kg_status sst = ensure_sets(s, p);  // before anything of the batch's result state changes
+        if (sst != KG_OK) return sst;
+    }
     p->k_last = k;
     p->kk_last = kk;
     if (p->n == 0) return KG_OK;
@@ -2654,9 +2877,12 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     uint32_t parts = 0;
     // one lane per distinct input row when that saves waves (dedup_on); k_expand_keys then serves the duplicates
     const bool dd = dedup_on(p);
-    LaunchSelect a = make_select(s, p->dev, dd ? p->d_rorder : p->d_order, dd ? p->n_rep : p->n,
-                                 dd ? p->n_rep_fast : p->n_fast, p->n, kk, true, d_out, nullptr, p->d_pstat, &parts);
-    if (select_small(s, a)) {
+    // a batch with candidate node sets: these lists hold the lanes without a set only (the full lists otherwise)
+    const uint32_t n_lanes = dd ? p->n_rep_plain : p->n_plain_lanes, n_lanes_fast = dd ? p->n_rep_plain_fast : p->n_plain_fast;
+    LaunchSelect a = make_select(s, p->dev, dd ? p->d_rorder : p->d_order, n_lanes, n_lanes_fast, p->n, kk, true, d_out,
+                                 nullptr, p->d_pstat, &parts);
+    // the one-pod-block select writes every row of out and pstat through the lane tables: not with sets
+    if (!p->any_set && select_small(s, a)) {
         // one launch (or two) writes every row of d_out and d_pstat: no memset, no side stream, no expansion
         const uint32_t lp = (a.n_fast + 63) / 64 * 64;
         kg_status st;
@@ -2719,6 +2945,8 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         return st;
     }
     HIP_TRY(ctx, hipMemsetAsync(p->d_pstat, 0, sizeof(uint32_t) * p->n, ctx->stream));
+    // the set lanes insert into zeroed rows by atomics, whichever form the other lanes' launch takes
+    if (p->any_set) HIP_TRY(ctx, hipMemsetAsync(d_out, 0, sizeof(uint64_t) * kk * p->n, ctx->stream));
     kg_status st = ensure_partial(p, std::max<size_t>((size_t)parts * p->n * kk, 1));
     if (st != KG_OK) return st;
     a.partial = p->d_partial;
@@ -2761,11 +2989,17 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     hipEvent_t e0, e1;
     st = record_begin(ctx, &e0, &e1);
     if (st != KG_OK) return st;
-    const hipError_t le = launch_select(a, ctx->stream);
+    const hipError_t le = a.n_pods ? launch_select(a, ctx->stream) : hipSuccess;
     // a launch error after the fork leaves the pruned lanes' kernels unjoined: drain the side stream before anything
     // later on ctx->stream (an upload into the pod columns, a free) can overtake them
     if (le != hipSuccess && a.side) hipStreamSynchronize(a.side);
     HIP_TRY(ctx, le);
+    // the lanes with a candidate node set (kg_sets.hip), on the main stream after the join
+    if (p->any_set)
+        HIP_TRY(ctx, launch_select_sets(s->d_nodes, s->d_zones, p->dev, dd ? p->d_srorder : p->d_sorder,
+                                        dd ? p->n_rep_set : p->n_set_lanes, p->sets_dev(), s->n0, s->n, s->base, kk, s->kcfg,
+                                        a.exact, !a.exact && !force_int() && s->weights_small, d_out, p->d_pstat,
+                                        ctx->stream));
     // after the side-stream join: every consumer (kg_result_keys, the all-gather, kg_result_status) sees whole tables
     if (dd) HIP_TRY(ctx, launch_expand_keys(p->d_rep, p->n, kk, d_out, p->d_pstat, ctx->stream));
     return record_end(ctx, e0, e1);
@@ -2878,6 +3112,11 @@ std::vector<uint8_t> replay_key(const kg_snap* s, const kg_pods* p, bool exact, 
     put(&s->d_cpu_alloc, sizeof(s->d_cpu_alloc));
     put(&s->d_cpu_topos, sizeof(s->d_cpu_topos));
     put(&s->d_pos, sizeof(s->d_pos));
+    // a batch with candidate node sets replays through other kernel instantiations, over its own tables
+    const int32_t* ps = p->any_set ? p->d_pod_set : nullptr;
+    const uint64_t* tab = p->any_set ? p->d_set_tab : nullptr;
+    put(&ps, sizeof(ps));
+    put(&tab, sizeof(tab));
     return k;
 }
 
@@ -2903,7 +3142,8 @@ kg_status replay_graph(kg_snap* s, kg_pods* p, bool exact, bool reasons) {
                                       ctx->stream);
         if (e == hipSuccess)
             e = launch_replay_step(s->d_nodes, s->d_zones, p->dev, p->n, s->n, s->base, s->kcfg, exact, p->d_step, t,
-                                   p->d_winners, s->d_zsel, reasons ? p->d_reason : nullptr, ctx->stream);
+                                   p->d_winners, s->d_zsel, reasons ? p->d_reason : nullptr, ctx->stream,
+                                   p->any_set ? p->d_pod_set : nullptr, p->d_set_tab, sets_words(s->n));
     }
     if (e == hipSuccess) e = launch_bump(p->d_step, REPLAY_G, ctx->stream);
     hipError_t ec = hipStreamEndCapture(ctx->stream, &graph);
@@ -3093,14 +3333,21 @@ kg_status kg_replay(kg_snap* s, kg_pods* p, int32_t* out_node, int64_t* out_tota
     if (rsv_numa_batch(s, p))
         return fail(ctx, KG_UNSUPPORTED, "replay over nodes whose reservations hold NUMA / cpuset allocations "
                                          "(kg_node_columns.rsv_numa) with pods that bind CPUs or a NUMA policy");
-    if (s->ext()) return ext_replay(s, p, out_node, out_total, out_reason);
+    if (s->ext()) {
+        st = refuse_sets(s, p, "replay on a snapshot with config-5 tables");
+        return st != KG_OK ? st : ext_replay(s, p, out_node, out_total, out_reason);
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = ensure_sets(s, p);
+    if (st != KG_OK) return st;
     const uint32_t n = p->n;
     const bool exact = force_exact();
     const bool reasons = out_reason != nullptr;
     // window replay needs the changed-row bitmap in LDS; every config-3 plugin scores a pair from its own row.
     // The FitError diagnosis (out_reason) needs every node's status in each pod's cycle: one pod per launch.
-    const bool windows = !reasons && !force_step_replay() && !cpuset_active(s, p) && s->n <= 32u * (uint32_t)RB_BITMAP_WORDS;
+    // A batch with candidate node sets takes the one-pod-per-launch form too (the windows are not extended).
+    const bool windows = !reasons && !force_step_replay() && !cpuset_active(s, p) && !p->any_set &&
+                         s->n <= 32u * (uint32_t)RB_BITMAP_WORDS;
     st = windows ? rb_graph(s, p, exact) : replay_graph(s, p, exact, reasons);
     if (st != KG_OK) return st;
     HIP_TRY(ctx, hipMemsetAsync(p->d_winners, 0, sizeof(uint64_t) * (n + 1), ctx->stream));
@@ -4242,6 +4489,8 @@ kg_status kg_shard_select(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* out_keys
     if (st != KG_OK) return st;
     kg_ctx* ctx = s->ctx;
     std::lock_guard<std::mutex> g(ctx->mu);
+    st = refuse_sets(s, p, "sharded select");  // the shards' exchange does not carry the sets
+    if (st != KG_OK) return st;
     if (!ctx->comm) return fail(ctx, KG_INVALID_ARG, "kg_shard_init not called");
     if (k == 0 || k > (uint32_t)KG_TOPK_MAX) return fail(ctx, KG_INVALID_ARG, "k=%u outside [1, %d]", k, KG_TOPK_MAX);
     st = check_views(s);

@@ -75,6 +75,8 @@ def lib():
     L.kg_pods_upload.restype = st
     L.kg_pods_select_lanes.argtypes = [vp, P(u32), P(u32)]
     L.kg_pods_select_lanes.restype = st
+    L.kg_pods_set_node_sets.argtypes = [vp, P(abi.KgNodeSets)]  # new within ABI 14: resolved here, at load time
+    L.kg_pods_set_node_sets.restype = st
     L.kg_pods_destroy.argtypes = [vp]
     L.kg_pods_destroy.restype = st
     L.kg_eval_verify.argtypes = [vp, vp, P(abi.KgVerifyOut)]
@@ -357,6 +359,23 @@ class PodBatch:
             cols = abi.pod_columns(pods)
             self._cols, self._cols_key = cols, (pods, tuple(pods.values()))
         self.ctx.check(self.ctx.L.kg_pods_upload(self.h, C.byref(cols), self.n), "kg_pods_upload")
+
+    def set_node_sets(self, pod_set, bits, n_nodes: int):
+        """kg_pods_set_node_sets: pod_set[j] = the candidate node set of pod j (-1: every node), bits[set] = its
+        bitmap over the n_nodes snapshot positions, 32 nodes per uint32 word (koordinator_amd.nodesets builds both).
+        Copied; the next upload() clears the sets."""
+        pod_set = np.ascontiguousarray(pod_set, np.int32).reshape(-1)
+        if len(pod_set) != self.n:
+            raise ValueError(f"pod_set has {len(pod_set)} entries for {self.n} pods")
+        words = (int(n_nodes) + 31) // 32
+        bits = np.ascontiguousarray(bits, np.uint32).reshape(-1, words) if words else np.zeros((0, 0), np.uint32)
+        sets = abi.KgNodeSets(
+            (pod_set if self.n else np.zeros(1, np.int32)).ctypes.data_as(C.POINTER(C.c_int32)),
+            bits.ctypes.data_as(C.POINTER(C.c_uint32)) if bits.size else None, len(bits), int(n_nodes))
+        self.ctx.check(self.ctx.L.kg_pods_set_node_sets(self.h, C.byref(sets)), "kg_pods_set_node_sets")
+
+    def clear_node_sets(self):
+        self.ctx.check(self.ctx.L.kg_pods_set_node_sets(self.h, None), "kg_pods_set_node_sets")
 
     def select_lanes(self):
         """kg_pods_select_lanes: (lanes, fast lanes) the next plain select launches (fewer than n when equal rows share

@@ -63,17 +63,24 @@ RSV_TABLE = (
     (abi.KG_ST_RSV_RESERVATION, "node(s) no reservation(s) to meet the requirements"),
 )
 QUOTA_REASON = "Insufficient quotas, <quota state>"
+# The node is outside the pod's candidate node set (kg_pods_set_node_sets). The Filter that excluded it ran on the host
+# (nodeSelector / affinity, taints, spec.nodeName, PodTopologySpread, ...) and owns the wording: pass its text as
+# excluded_reason= where the exact FitError matters.
+EXCLUDED_REASON = "node(s) excluded from the pod's candidates"
 HOST_PATH_REASON = "pair evaluated by the reference plugin on the host"
 
 
-def plugin_reasons(bits: int, scalar_names=DEFAULT_SCALARS) -> dict:
-    """{plugin name: [reason, ...]} of one status word (or an OR of several)."""
+def plugin_reasons(bits: int, scalar_names=DEFAULT_SCALARS, excluded_reason=None) -> dict:
+    """{plugin name: [reason, ...]} of one status word (or an OR of several). excluded_reason: the wording of
+    KG_ST_NODE_EXCLUDED, which belongs to the host Filter that narrowed the pod's nodes (default EXCLUDED_REASON)."""
     bits = int(bits)
     out: dict = {}
 
     def add(plugin, msg):
         out.setdefault(plugin, []).append(msg)
 
+    if bits & abi.KG_ST_NODE_EXCLUDED:  # the host's Filter ran before every koord plugin
+        add("(candidate nodes)", excluded_reason or EXCLUDED_REASON)
     for bit, msg in _nrf_table(scalar_names):
         if bits & bit:
             add("NodeResourcesFit", msg)
@@ -115,16 +122,16 @@ DEV_CODE_REASONS = {
 }
 
 
-def reasons(bits: int, scalar_names=DEFAULT_SCALARS) -> list:
+def reasons(bits: int, scalar_names=DEFAULT_SCALARS, excluded_reason=None) -> list:
     """Flat list of the reasons in plugin filter order."""
-    return [m for msgs in plugin_reasons(bits, scalar_names).values() for m in msgs]
+    return [m for msgs in plugin_reasons(bits, scalar_names, excluded_reason).values() for m in msgs]
 
 
 def _slot(bit: int) -> int:
     return int(bit).bit_length() - 1
 
 
-def reason_counts(counts_row, scalar_names=DEFAULT_SCALARS) -> dict:
+def reason_counts(counts_row, scalar_names=DEFAULT_SCALARS, excluded_reason=None) -> dict:
     """{reason string: number of nodes} of one row of engine.eval_diagnose (kg_eval_diagnose): the histogram the
     framework's FitError prints. The strings are plugin_reasons'; DeviceShare's come from the code slots
     (KG_DIAG_DEV_CODE0 + code), not from the code's raw bits; bits that map to one string add up; zero counts are
@@ -143,6 +150,7 @@ def reason_counts(counts_row, scalar_names=DEFAULT_SCALARS) -> dict:
         if n:
             out[msg] = out.get(msg, 0) + n
 
+    add(excluded_reason or EXCLUDED_REASON, c[_slot(abi.KG_ST_NODE_EXCLUDED)])
     for bit, msg in _nrf_table(scalar_names):
         add(msg, c[_slot(bit)])
     add(LA_EXPIRED_REASON, c[_slot(abi.KG_ST_LA_EXPIRED)])
@@ -165,7 +173,7 @@ def reason_counts(counts_row, scalar_names=DEFAULT_SCALARS) -> dict:
     return out
 
 
-def fit_error(counts_row, n_nodes: int, scalar_names=DEFAULT_SCALARS, prefilter_msg=None) -> str:
+def fit_error(counts_row, n_nodes: int, scalar_names=DEFAULT_SCALARS, prefilter_msg=None, excluded_reason=None) -> str:
     """The text of upstream's FitError.Error() (k8s.io/kubernetes pkg/scheduler/framework/types.go) for one row of
     first-plugin counts (engine.eval_diagnose(first_plugin=True): the framework records one failing plugin per node):
     "0/<n_nodes> nodes are available: " + the "<count> <reason>" items sorted as strings, joined by ", " + ".";
@@ -175,7 +183,7 @@ def fit_error(counts_row, n_nodes: int, scalar_names=DEFAULT_SCALARS, prefilter_
     head = f"0/{int(n_nodes)} nodes are available:"
     if int(counts_row[_slot(abi.KG_ST_QUOTA)]):
         return f"{head} {prefilter_msg or QUOTA_REASON}."
-    items = sorted(f"{n} {msg}" for msg, n in reason_counts(counts_row, scalar_names).items())
+    items = sorted(f"{n} {msg}" for msg, n in reason_counts(counts_row, scalar_names, excluded_reason).items())
     return f"{head} {', '.join(items)}." if items else head
 
 
