@@ -29,6 +29,7 @@
 
 #include "../../include/koordgpu.h"
 #include "kg_dedup.h"
+#include "kg_devmem.h"
 #include "kg_diag.h"
 #include "kg_kernels.h"
 #include "kg_layout.h"
@@ -50,12 +51,11 @@ struct kg_ctx {
     // of the device's wall clock, allocated and zeroed at the first such select and never reset; prof_seen = the words at
     // the last kg_profile_read; prof_pending = launches handed d_prof since then; clock_khz = that clock's rate
     // (hipDeviceAttributeWallClockRate; -1: not queried yet, 0: not available, the bound event pair stays).
-    uint64_t* d_prof = nullptr;
+    DevBuf<uint64_t> d_prof;
     uint64_t prof_seen[2] = {0, 0};
     uint64_t prof_pending = 0;
     int clock_khz = -1;
-    uint64_t* d_phases = nullptr;  // KG_SMALL_PHASES: per-workgroup clock readings of one launch (measurement aid)
-    size_t phases_cap = 0;
+    DevBuf<uint64_t> d_phases;  // KG_SMALL_PHASES: per-workgroup clock readings of one launch (measurement aid)
     int cus = -1;  // compute units of the device (device_cus), queried on first use
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
@@ -72,11 +72,11 @@ struct kg_snap {
     kg_config cfg{};
     KCfg kcfg{};
     uint32_t n = 0, base = 0;
-    NodeRec* d_nodes = nullptr;
-    ZoneRec* d_zones = nullptr;
-    uint32_t* d_big = nullptr;  // [0] = count, [1..] = list of F_BIG records (k_big_scan)
-    int8_t* d_zsel = nullptr;   // replay: NUMA zone each record chose for the current pod
-    uint32_t* d_pos = nullptr;  // snapshot index -> record position (block replay)
+    DevBuf<NodeRec> d_nodes;
+    DevBuf<ZoneRec> d_zones;
+    DevBuf<uint32_t> d_big;  // [0] = count, [1..] = list of F_BIG records (k_big_scan)
+    DevBuf<int8_t> d_zsel;   // replay: NUMA zone each record chose for the current pod
+    DevBuf<uint32_t> d_pos;  // snapshot index -> record position (block replay)
     // Records are stored grouped by storage class (node_class: 0 = no per-zone scoring, 1 = NUMA
     // SingleNUMANode), each group in ascending snapshot index; the high half of v[N_FLAGS] holds the snapshot index.
     std::vector<NodeRec> h_nodes;  // device order
@@ -88,20 +88,20 @@ struct kg_snap {
     bool uploaded = false;
     bool weights_small = false;  // per-resource weights <= 2^12: float64 fast path allowed
     // config-5 tables (KG_PLUGIN_DEV / RSV / QUOTA)
-    DevRec* d_dev = nullptr;       // [record]
+    DevBuf<DevRec> d_dev;       // [record]
     std::vector<DevRec> h_dev;     // device order
-    QuotaLim* d_qlim = nullptr;
-    QuotaState* d_qstate = nullptr;  // [2][n_quotas]
+    DevBuf<QuotaLim> d_qlim;
+    DevBuf<QuotaState> d_qstate;  // [2][n_quotas]
     uint32_t n_quotas = 0;
-    RsvView* d_views = nullptr;
-    uint32_t* d_vfirst = nullptr;  // ExtDev::vfirst / vmap
-    uint32_t* d_vmap = nullptr;
-    RsvInfo* d_infos = nullptr;
-    uint32_t* d_cls_begin = nullptr;  // [RSV_MAX_CLASSES + 1]
-    DevRec* d_rdev = nullptr;         // kg_rsv_dev tables
-    uint32_t* d_rdev_rec = nullptr;   // record (position) of the node each kg_rsv_dev table belongs to
+    DevBuf<RsvView> d_views;
+    DevBuf<uint32_t> d_vfirst;  // ExtDev::vfirst / vmap
+    DevBuf<uint32_t> d_vmap;
+    DevBuf<RsvInfo> d_infos;
+    DevBuf<uint32_t> d_cls_begin;  // [RSV_MAX_CLASSES + 1]
+    DevBuf<DevRec> d_rdev;         // kg_rsv_dev tables
+    DevBuf<uint32_t> d_rdev_rec;   // record (position) of the node each kg_rsv_dev table belongs to
     uint32_t n_rdev = 0;
-    uint32_t* d_special = nullptr;    // [0] = count, [1..]: records the fast-base ext kernels leave to PART 2
+    DevBuf<uint32_t> d_special;    // [0] = count, [1..]: records the fast-base ext kernels leave to PART 2
     uint32_t n_view_nodes = 0;        // nodes holding a reservation view
     // PART 2 grid: the class-1 records and the largest reservation class's views (F_BIG records come on top)
     uint32_t special_est() const { return std::max(n - n0, max_cls_views); }
@@ -124,17 +124,17 @@ struct kg_snap {
     bool rsv_gpu = false, views_on_device = false;
     // DeviceShare restore inputs of the GPU-holding reservations (kg_snapshot_upload_rsv_gpu): with them the Reserves
     // follow those reservations on the device (gpu_restore_apply); an upload / update of the views drops them
-    int32_t* d_graw = nullptr;       // [record] GpuRawNode index, -1 = none
-    GpuRawNode* d_gnodes = nullptr;
-    GpuRawRsv* d_grsv = nullptr;
+    DevBuf<int32_t> d_graw;       // [record] GpuRawNode index, -1 = none
+    DevBuf<GpuRawNode> d_gnodes;
+    DevBuf<GpuRawRsv> d_grsv;
     uint32_t n_gnodes = 0, n_grsv = 0;
     bool gpu_raw = false;
     // a Reserve can follow every reservation of the snapshot on the device (none holds GPUs, or their inputs are here)
     bool rsv_follow() const { return !rsv_gpu || gpu_raw; }
     std::vector<uint32_t> view_order;  // device view t -> h_views index
-    int32_t* d_nsel = nullptr;         // replay: nominated reservation of each record's pair (2 x n, like d_zsel)
-    RsvStep* d_rstep = nullptr;        // replay with views: [3] per-step Reservation normalisation and winner
-    uint64_t* d_rlist = nullptr;       // replay with views: [3][n] pairs with a Reservation score term (2 x u64)
+    DevBuf<int32_t> d_nsel;         // replay: nominated reservation of each record's pair (2 x n, like d_zsel)
+    DevBuf<RsvStep> d_rstep;        // replay with views: [3] per-step Reservation normalisation and winner
+    DevBuf<uint64_t> d_rlist;       // replay with views: [3][n] pairs with a Reservation score term (2 x u64)
     // Generation: bumped by every call that changes what the snapshot holds (upload, row update, Assume /
     // Forget, replay, quota / reservation upload); kg_snapshot_generation reads it.
     uint64_t gen = 0;
@@ -143,25 +143,25 @@ struct kg_snap {
     // record-order table of candidate node sets is valid for one (uid, layout); gen does not serve: every Reserve bumps it.
     uint64_t uid = 0, layout = 0;
     // batched row updates: staged records (NodeRec, ZoneRec[, DevRec] per row) and their positions
-    uint8_t* d_stage = nullptr;
-    uint32_t* d_stage_pos = nullptr;
+    DevBuf<uint8_t> d_stage;
+    DevBuf<uint32_t> d_stage_pos;
     size_t stage_cap = 0;  // rows
     std::vector<uint8_t> h_stage;
     // Saved Reserve state: `ck` for kg_snapshot_checkpoint / rollback (planners), `bk` for the cleanup of a
     // failed kg_batch_schedule. Invalidated by anything that may move records or replace tables.
     struct Saved {
-        NodeRec* nodes = nullptr;
-        ZoneRec* zones = nullptr;
-        DevRec* dev = nullptr;
-        kg_cpu_alloc* cpu = nullptr;
-        QuotaState* q = nullptr;
+        DevBuf<NodeRec> nodes;
+        DevBuf<ZoneRec> zones;
+        DevBuf<DevRec> dev;
+        DevBuf<kg_cpu_alloc> cpu;
+        DevBuf<QuotaState> q;
         uint32_t nq = 0;
-        RsvView* views = nullptr;  // the views and reservations Reservation.Reserve changes on the device
-        RsvInfo* infos = nullptr;
+        DevBuf<RsvView> views;  // the views and reservations Reservation.Reserve changes on the device
+        DevBuf<RsvInfo> infos;
         uint32_t nv = 0, ni = 0;
-        DevRec* rdev = nullptr;  // GPU restore tables and their raw inputs (GPU-holding reservations)
-        GpuRawNode* gnodes = nullptr;
-        GpuRawRsv* grsv = nullptr;
+        DevBuf<DevRec> rdev;  // GPU restore tables and their raw inputs (GPU-holding reservations)
+        DevBuf<GpuRawNode> gnodes;
+        DevBuf<GpuRawRsv> grsv;
         uint32_t nrd = 0, ngn = 0, ngr = 0;
         bool views_on_device = false;
         bool valid = false, views_stale = false;
@@ -170,16 +170,16 @@ struct kg_snap {
     } ck, bk;
     void invalidate_saved() { ck.valid = bk.valid = false; }
     // cpuset binding: CPU topology table, per-record allocations (device order, like h_dev)
-    kg_cpu_topo* d_cpu_topos = nullptr;
+    DevBuf<kg_cpu_topo> d_cpu_topos;
     uint32_t n_cpu_topos = 0;
-    kg_cpu_alloc* d_cpu_alloc = nullptr;
+    DevBuf<kg_cpu_alloc> d_cpu_alloc;
     std::vector<kg_cpu_alloc> h_cpu_alloc;
     bool has_cpu = false;   // the snapshot carries CPU topologies
     bool node_bind = false; // some node has a CPU bind policy (every pod with a cpu request binds there)
     // GPU partition tables (kg_node_columns.gpu_parts): entries and per (table, GPU count) ranges
-    kg_gpu_partition* d_parts = nullptr;
-    uint32_t* d_part_rng = nullptr;  // [KG_GPU_MAX_TABLES * 9]
-    int64_t* d_binpack = nullptr;    // [KG_GPU_MAX_TABLES][3][256]
+    DevBuf<kg_gpu_partition> d_parts;
+    DevBuf<uint32_t> d_part_rng;  // [KG_GPU_MAX_TABLES * 9]
+    DevBuf<int64_t> d_binpack;    // [KG_GPU_MAX_TABLES][3][256]
     uint32_t n_gpu_tables = 0, n_gpu_parts = 0;
     bool ext() const { return (cfg.plugins & KG_PLUGIN_EXT) != 0; }
     ExtDev ext_dev() const {
@@ -210,8 +210,8 @@ struct kg_pods {
     uint32_t cap = 0, n = 0;
     // Inputs of the batch: one device blob filled from pinned staging by one copy per upload, regions in
     // pod_layout(n) order; the PodsDev and list pointers below point into it for the current batch.
-    uint8_t* d_in = nullptr;
-    uint8_t* h_in = nullptr;  // pinned host staging of the same size
+    DevBuf<uint8_t> d_in;
+    PinnedBuf<uint8_t> h_in;  // pinned host staging of the same size
     hipEvent_t in_copied = nullptr;  // the last upload's copy out of h_in (the next upload rewrites h_in after it)
     bool in_pending = false;
     uint32_t defaults_n = 0;  // the config-5 regions hold the absent-column defaults for a batch of this size (0: no)
@@ -242,39 +242,33 @@ struct kg_pods {
     uint32_t n_stat_cls = 0;          // leading d_stat_list entries without a GPU request (class views only)
     uint32_t n_plain = 0, n_x = 0;
     // select results
-    uint64_t* d_partial = nullptr;
-    uint64_t* d_ipairs = nullptr;       // pruned integer lanes: surviving (lane, record) pairs (LaunchSelect.ipairs)
-    uint32_t* d_ipair_count = nullptr;
+    DevBuf<uint64_t> d_partial;
+    DevBuf<uint64_t> d_ipairs;       // pruned integer lanes: surviving (lane, record) pairs (LaunchSelect.ipairs)
+    DevBuf<uint32_t> d_ipair_count;
     size_t ipairs_cap = 0;
-    size_t partial_cap = 0;  // entries
     // accumulators and ticket of the one-launch one-pod-block select: all zero between selects (ensure_sacc)
-    uint8_t* d_sacc = nullptr;
-    size_t sacc_cap = 0;  // bytes
+    DevBuf<uint8_t> d_sacc;
     bool sacc_dirty = false;
-    uint64_t* d_keys = nullptr;
+    DevBuf<uint64_t> d_keys;
     uint32_t k_last = 0, kk_last = 0;
-    uint64_t* h_keys = nullptr;    // pinned download staging of the keys [cap][KG_TOPK_MAX]
-    uint32_t* d_pstat = nullptr;   // per pod: KG_ST_UNSUPPORTED / KG_ST_QUOTA of the last select (kg_result_status)
-    uint32_t* d_reason = nullptr;  // replay: per pod OR of the filter status bits (kg_replay out_reason)
+    PinnedBuf<uint64_t> h_keys;    // pinned download staging of the keys [cap][KG_TOPK_MAX]
+    DevBuf<uint32_t> d_pstat;   // per pod: KG_ST_UNSUPPORTED / KG_ST_QUOTA of the last select (kg_result_status)
+    DevBuf<uint32_t> d_reason;  // replay: per pod OR of the filter status bits (kg_replay out_reason)
     // kg_eval_diagnose: the requested rows and their KG_DIAG_SLOTS counters, grown on demand (ensure_diag)
-    uint32_t* d_diag_rows = nullptr;
-    uint32_t* d_diag = nullptr;
+    DevBuf<uint32_t> d_diag_rows;
+    DevBuf<uint32_t> d_diag;
     size_t diag_cap = 0;  // rows
-    DevSum* d_devsum = nullptr;    // per record DevSum of the last config-5 select
-    size_t devsum_cap = 0;
-    uint64_t* d_gz = nullptr;      // gpu_zone_sum per (class-1 record, GPU request class) of the last config-5 select
-    size_t gz_cap = 0;
-    uint8_t* d_rcode = nullptr;    // [kg_rsv_dev table][DEV_CLASSES]: GPU allocator outcome on the restore tables
-    size_t rcode_cap = 0;
+    DevBuf<DevSum> d_devsum;    // per record DevSum of the last config-5 select
+    DevBuf<uint64_t> d_gz;      // gpu_zone_sum per (class-1 record, GPU request class) of the last config-5 select
+    DevBuf<uint8_t> d_rcode;    // [kg_rsv_dev table][DEV_CLASSES]: GPU allocator outcome on the restore tables
     // one-pass fast-base select of the GPU pods (ExtDev.cls_max / fb_max / rows): [cap] fast-base maxima, [cap] rows
     // to re-run, [DEV_CLASSES] per-class bounds, row count
-    uint32_t* d_spec = nullptr;
-    int64_t* d_split = nullptr;  // kg_assume_numa / kg_forget_numa: per-zone amounts of a NUMA allocation
+    DevBuf<uint32_t> d_spec;
+    DevBuf<int64_t> d_split;  // kg_assume_numa / kg_forget_numa: per-zone amounts of a NUMA allocation
     // replay / shard scratch
-    uint64_t* d_winners = nullptr;
-    uint32_t* d_step = nullptr;
-    uint64_t* d_gather = nullptr;
-    size_t gather_cap = 0;
+    DevBuf<uint64_t> d_winners;
+    DevBuf<uint32_t> d_step;
+    DevBuf<uint64_t> d_gather;
     bool fast_ok = false;  // every pod in the fast domain (no value >= 2^44, no pod NUMA policy, no cpuset binding)
     bool pod_policy = false;  // some pod carries its own NUMA policy
     bool any_cpu_bind = false;  // some pod binds cpusets (KG_POD_CPU_BIND)
@@ -282,29 +276,27 @@ struct kg_pods {
     std::vector<uint32_t> h_flags;  // host copies for argument checks (kg_forget of a cpuset pod)
     std::vector<int64_t> h_req_cpu;
     // config-5 scratch
-    uint32_t* d_qst = nullptr;        // ElasticQuota PreFilter status per pod
-    uint32_t* d_dev_max = nullptr;    // [cap] pass-1 NormalizeScore maxima
-    uint32_t* d_rsv_max = nullptr;
-    uint64_t* d_pref = nullptr;
-    uint32_t* d_minors = nullptr;     // replay: GPU minors chosen per pod
-    uint64_t* d_buckets = nullptr;    // replay: [3][128] per-score best keys (REPLAY_BUCKET_STRIDE apart)
-    uint32_t* d_done = nullptr;       // config-5 replay: workgroups done in the current step launch (last one picks)
-    uint64_t* d_xpairs = nullptr;     // fast-base config-5 select: stored general pairs (ExtDev::xpairs)
-    size_t xpairs_cap = 0;            // entries
+    DevBuf<uint32_t> d_qst;        // ElasticQuota PreFilter status per pod
+    DevBuf<uint32_t> d_dev_max;    // [cap] pass-1 NormalizeScore maxima
+    DevBuf<uint32_t> d_rsv_max;
+    DevBuf<uint64_t> d_pref;
+    DevBuf<uint32_t> d_minors;     // replay: GPU minors chosen per pod
+    DevBuf<uint64_t> d_buckets;    // replay: [3][128] per-score best keys (REPLAY_BUCKET_STRIDE apart)
+    DevBuf<uint32_t> d_done;       // config-5 replay: workgroups done in the current step launch (last one picks)
+    DevBuf<uint64_t> d_xpairs;     // fast-base config-5 select: stored general pairs (ExtDev::xpairs)
     uint32_t xT = 0;                  // row length of the pairs the last ext_stats_local stored (0 = none)
-    int32_t* d_aout = nullptr;        // kg_assume_ext outputs
-    uint64_t* d_rec = nullptr;        // kg_reserve / kg_unreserve: cpuset CPUs [4] + NUMA zone amounts [8]
-    uint32_t* d_batch = nullptr;      // kg_batch_schedule: groups + per-pod outputs (7 x cap + 1 words)
+    DevBuf<int32_t> d_aout;        // kg_assume_ext outputs
+    DevBuf<uint64_t> d_rec;        // kg_reserve / kg_unreserve: cpuset CPUs [4] + NUMA zone amounts [8]
+    DevBuf<uint32_t> d_batch;      // kg_batch_schedule: groups + per-pod outputs (7 x cap + 1 words)
     hipGraphExec_t xexec = nullptr;   // ext replay graph
     std::vector<uint8_t> xkey;
-    uint64_t* d_tkeys = nullptr;  // [KG_TOPK_MAX][cap] config-5 sub-batch keys before the scatter
+    DevBuf<uint64_t> d_tkeys;  // [KG_TOPK_MAX][cap] config-5 sub-batch keys before the scatter
     // replay graph (G steps) cached for the (snapshot buffers, batch size, configuration) it captured
     hipGraphExec_t rexec = nullptr;
     std::vector<uint8_t> rkey;
     // block replay: per-window chunk lists and merged lists, graph of RB_R windows
-    uint64_t* d_rbpart = nullptr;
-    size_t rbpart_cap = 0;  // entries
-    uint64_t* d_rbtops = nullptr;
+    DevBuf<uint64_t> d_rbpart;
+    DevBuf<uint64_t> d_rbtops;
     hipGraphExec_t bexec = nullptr;
     std::vector<uint8_t> bkey;
     LaunchRb rb_args{};
@@ -319,12 +311,11 @@ struct kg_pods {
     std::vector<uint32_t> h_set_bits; // [n_sets][words32], tail bits cleared
     uint32_t set_n_sets = 0, set_n_nodes = 0;
     uint32_t n_plain_lanes = 0, n_plain_fast = 0, n_rep_plain = 0, n_rep_plain_fast = 0, n_set_lanes = 0, n_rep_set = 0;
-    int32_t* d_pod_set = nullptr;     // [cap]
-    uint32_t* d_sorder = nullptr;     // [cap]
-    uint32_t* d_srorder = nullptr;    // [cap]
-    uint32_t* d_set_bits = nullptr;
-    uint64_t* d_set_tab = nullptr;    // [n_sets][words]: record order, for (tab_uid, tab_layout)
-    size_t set_bits_cap = 0, set_tab_cap = 0;  // words
+    DevBuf<int32_t> d_pod_set;     // [cap]
+    DevBuf<uint32_t> d_sorder;     // [cap]
+    DevBuf<uint32_t> d_srorder;    // [cap]
+    DevBuf<uint32_t> d_set_bits;
+    DevBuf<uint64_t> d_set_tab;    // [n_sets][words]: record order, for (tab_uid, tab_layout)
     bool tab_valid = false;
     uint64_t tab_uid = 0, tab_layout = 0;
     SetsDev sets_dev() const {
@@ -338,6 +329,12 @@ struct kg_pods {
         return d;
     }
 };
+
+// The allocation seam of kg_devmem.h: the only HIP allocation calls of the runtime.
+int kg::dev_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+int kg::dev_free(void* p) { return hipFree(p); }
+int kg::pinned_alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+int kg::pinned_free(void* p) { return hipHostFree(p); }
 
 // ------------------------------------------------------------------------------------------------
 namespace {
@@ -354,11 +351,28 @@ kg_status fail(kg_ctx* ctx, kg_status s, const char* fmt, ...) {
 
 #define HIP_TRY(ctx, expr)                                                                                     \
     do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
+        hipError_t e_ = static_cast<hipError_t>(expr); /* a DevBuf call returns the hipError_t as int */        \
         if (e_ != hipSuccess)                                                                                  \
             return fail((ctx), e_ == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR, "%s: %s (%s:%d)", #expr, \
                         hipGetErrorString(e_), __FILE__, __LINE__);                                            \
     } while (0)
+
+// Grow b to n elements (contents not kept). The one rule of every grow site: a kernel or copy still in flight on the
+// context's stream may read the old allocation, so the stream is drained before it is freed.
+template <class T>
+int grow(kg_ctx* ctx, DevBuf<T>& b, size_t n) {
+    if (b.cap() >= n) return hipSuccess;
+    if (b)
+        if (hipError_t e = hipStreamSynchronize(ctx->stream)) return e;
+    return b.reserve(n);
+}
+
+// Replace b by a fresh allocation of exactly n elements: the tables an upload rebuilds. The caller has drained the stream.
+template <class T>
+int renew(DevBuf<T>& b, size_t n) {
+    const int e = b.reset();
+    return e ? e : b.alloc(n);
+}
 
 #define NCCL_TRY(ctx, expr)                                                                                    \
     do {                                                                                                       \
@@ -916,8 +930,6 @@ kg_status kg_close(kg_ctx* ctx) {
         hipEventDestroy(e.first);
         hipEventDestroy(e.second);
     }
-    if (ctx->d_prof) hipFree(ctx->d_prof);
-    if (ctx->d_phases) hipFree(ctx->d_phases);
     if (ctx->side) hipStreamDestroy(ctx->side);
     if (ctx->fork) hipEventDestroy(ctx->fork);
     if (ctx->join) hipEventDestroy(ctx->join);
@@ -970,21 +982,13 @@ kg_status kg_snapshot_create(kg_ctx* ctx, const kg_config* cfg, uint32_t n_nodes
     s->h_nodes.resize(n_nodes);
     s->h_zones.resize(n_nodes);
     hipSetDevice(ctx->device);
-    const size_t nb = sizeof(NodeRec) * std::max<uint32_t>(n_nodes, 1), zb = sizeof(ZoneRec) * std::max<uint32_t>(n_nodes, 1);
-    if (hipMalloc(&s->d_nodes, nb) != hipSuccess || hipMalloc(&s->d_zones, zb) != hipSuccess ||
-        hipMalloc(&s->d_big, sizeof(uint32_t) * ((size_t)n_nodes + 1)) != hipSuccess ||
-        hipMalloc(&s->d_zsel, 2 * (size_t)std::max<uint32_t>(n_nodes, 1)) != hipSuccess ||
-        hipMalloc(&s->d_nsel, sizeof(int32_t) * 2 * (size_t)std::max<uint32_t>(n_nodes, 1)) != hipSuccess ||
-        hipMalloc(&s->d_pos, sizeof(uint32_t) * std::max<uint32_t>(n_nodes, 1)) != hipSuccess ||
-        hipMemset(s->d_big, 0, sizeof(uint32_t)) != hipSuccess) {
-        hipFree(s->d_nodes);
-        hipFree(s->d_zones);
+    const size_t n1 = std::max<uint32_t>(n_nodes, 1);
+    if (s->d_nodes.alloc(n1) || s->d_zones.alloc(n1) || s->d_big.alloc((size_t)n_nodes + 1) || s->d_zsel.alloc(2 * n1) ||
+        s->d_nsel.alloc(2 * n1) || s->d_pos.alloc(n1) || hipMemset(s->d_big, 0, sizeof(uint32_t)) != hipSuccess) {
         delete s;
         return fail(ctx, KG_OOM, "snapshot of %u nodes", n_nodes);
     }
-    if ((cfg->plugins & KG_PLUGIN_DEV) && hipMalloc(&s->d_dev, sizeof(DevRec) * std::max<uint32_t>(n_nodes, 1)) != hipSuccess) {
-        hipFree(s->d_nodes);
-        hipFree(s->d_zones);
+    if ((cfg->plugins & KG_PLUGIN_DEV) && s->d_dev.alloc(n1)) {
         delete s;
         return fail(ctx, KG_OOM, "device tables of %u nodes", n_nodes);
     }
@@ -1032,13 +1036,13 @@ static kg_status upload_gpu_parts(kg_snap* s, const kg_node_columns* cols) {
                 bp[((size_t)tb * 3 + k) * 256 + mask] = sum;
             }
         }
-    if (!s->d_part_rng) HIP_TRY(ctx, hipMalloc(&s->d_part_rng, sizeof(uint32_t) * KG_GPU_MAX_TABLES * 9));
-    if (!s->d_binpack) HIP_TRY(ctx, hipMalloc(&s->d_binpack, sizeof(int64_t) * bp.size()));
+    HIP_TRY(ctx, s->d_part_rng.reserve(rng.size()));
+    HIP_TRY(ctx, s->d_binpack.reserve(bp.size()));
     HIP_TRY(ctx, hipMemcpyAsync(s->d_part_rng, rng.data(), sizeof(uint32_t) * rng.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(s->d_binpack, bp.data(), sizeof(int64_t) * bp.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the staging vectors go out of scope
     // fixed capacity, so the pointer a captured replay graph holds never changes (only the contents do)
-    if (!s->d_parts) HIP_TRY(ctx, hipMalloc(&s->d_parts, sizeof(kg_gpu_partition) * KG_GPU_MAX_PARTS));
+    HIP_TRY(ctx, s->d_parts.reserve(KG_GPU_MAX_PARTS));
     if (n) {
         HIP_TRY(ctx, hipMemcpyAsync(s->d_parts, cols->gpu_parts, sizeof(kg_gpu_partition) * n, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1061,16 +1065,12 @@ static kg_status upload_cpu_topos(kg_snap* s, const kg_node_columns* cols, uint3
     kg_ctx* ctx = s->ctx;
     for (uint32_t t = 0; t < cols->n_cpu_topos; t++)
         if (const char* why = cpu_topo_problem(cols->cpu_topos[t])) return fail(ctx, KG_UNSUPPORTED, "CPU topology %u: %s", t, why);
-    if (cols->n_cpu_topos > s->n_cpu_topos || !s->d_cpu_topos) {
-        hipFree(s->d_cpu_topos);
-        s->d_cpu_topos = nullptr;
-        HIP_TRY(ctx, hipMalloc(&s->d_cpu_topos, sizeof(kg_cpu_topo) * std::max<uint32_t>(cols->n_cpu_topos, 1)));
-    }
+    HIP_TRY(ctx, grow(ctx, s->d_cpu_topos, std::max<uint32_t>(cols->n_cpu_topos, 1)));
     if (cols->n_cpu_topos)
         HIP_TRY(ctx, hipMemcpyAsync(s->d_cpu_topos, cols->cpu_topos, sizeof(kg_cpu_topo) * cols->n_cpu_topos,
                                     hipMemcpyHostToDevice, ctx->stream));
     s->n_cpu_topos = std::max(s->n_cpu_topos, cols->n_cpu_topos);
-    if (!s->d_cpu_alloc) HIP_TRY(ctx, hipMalloc(&s->d_cpu_alloc, sizeof(kg_cpu_alloc) * std::max<uint32_t>(s->n, 1)));
+    HIP_TRY(ctx, s->d_cpu_alloc.reserve(std::max<uint32_t>(s->n, 1)));
     s->has_cpu = true;
     for (uint32_t i = 0; cols->cpu_bind_policy && i < n_rows; i++) s->node_bind |= cols->cpu_bind_policy[i] != 0;
     return KG_OK;
@@ -1224,14 +1224,9 @@ kg_status kg_snapshot_update_rows(kg_snap* s, const uint32_t* rows, uint32_t n, 
         // one staged copy of every changed record, then one scatter launch to their positions
         const size_t rb = sizeof(NodeRec) + sizeof(ZoneRec) + (dev ? sizeof(DevRec) : 0);
         if (n > s->stage_cap) {
-            hipFree(s->d_stage);
-            hipFree(s->d_stage_pos);
-            s->d_stage = nullptr;
-            s->d_stage_pos = nullptr;
             s->stage_cap = 0;
             const size_t cap = std::max<size_t>(n, 256);
-            if (hipMalloc(&s->d_stage, (sizeof(NodeRec) + sizeof(ZoneRec) + sizeof(DevRec)) * cap) != hipSuccess ||
-                hipMalloc(&s->d_stage_pos, sizeof(uint32_t) * cap) != hipSuccess)
+            if (grow(ctx, s->d_stage, (sizeof(NodeRec) + sizeof(ZoneRec) + sizeof(DevRec)) * cap) || grow(ctx, s->d_stage_pos, cap))
                 return fail(ctx, KG_OOM, "row-update staging for %u rows", n);
             s->stage_cap = cap;
         }
@@ -1337,47 +1332,6 @@ kg_status kg_snapshot_destroy(kg_snap* s) {
     if (!s) return KG_INVALID_ARG;
     hipSetDevice(s->ctx->device);
     hipStreamSynchronize(s->ctx->stream);
-    hipFree(s->d_nodes);
-    hipFree(s->d_zones);
-    hipFree(s->d_big);
-    hipFree(s->d_zsel);
-    hipFree(s->d_nsel);
-    hipFree(s->d_rstep);
-    hipFree(s->d_rlist);
-    hipFree(s->d_pos);
-    hipFree(s->d_dev);
-    hipFree(s->d_parts);
-    hipFree(s->d_part_rng);
-    hipFree(s->d_rdev_rec);
-    hipFree(s->d_binpack);
-    hipFree(s->d_qlim);
-    hipFree(s->d_qstate);
-    hipFree(s->d_views);
-    hipFree(s->d_vfirst);
-    hipFree(s->d_vmap);
-    hipFree(s->d_infos);
-    hipFree(s->d_cls_begin);
-    hipFree(s->d_rdev);
-    hipFree(s->d_special);
-    hipFree(s->d_stage);
-    hipFree(s->d_stage_pos);
-    for (kg_snap::Saved* k : {&s->ck, &s->bk}) {
-        hipFree(k->nodes);
-        hipFree(k->zones);
-        hipFree(k->dev);
-        hipFree(k->cpu);
-        hipFree(k->q);
-        hipFree(k->views);
-        hipFree(k->infos);
-        hipFree(k->rdev);
-        hipFree(k->gnodes);
-        hipFree(k->grsv);
-    }
-    hipFree(s->d_graw);
-    hipFree(s->d_gnodes);
-    hipFree(s->d_grsv);
-    hipFree(s->d_cpu_topos);
-    hipFree(s->d_cpu_alloc);
     delete s;
     return KG_OK;
 }
@@ -1476,32 +1430,16 @@ kg_status kg_pods_create(kg_ctx* ctx, uint32_t capacity, kg_pods** out) {
     p->cap = capacity;
     p->in_bytes = pod_layout(capacity).total;
     hipSetDevice(ctx->device);
-    bool ok = hipMalloc(&p->d_in, p->in_bytes) == hipSuccess &&
-              hipHostMalloc(&p->h_in, p->in_bytes, hipHostMallocDefault) == hipSuccess &&
-              hipMalloc(&p->d_keys, sizeof(uint64_t) * KG_TOPK_MAX * capacity) == hipSuccess &&
-              hipHostMalloc(&p->h_keys, sizeof(uint64_t) * KG_TOPK_MAX * capacity, hipHostMallocDefault) == hipSuccess &&
-              hipMalloc(&p->d_winners, sizeof(uint64_t) * (capacity + 1)) == hipSuccess &&
-              hipMalloc(&p->d_step, sizeof(uint32_t) * 64) == hipSuccess &&
-              hipMalloc(&p->d_qst, sizeof(uint32_t) * capacity) == hipSuccess &&
-              hipMalloc(&p->d_dev_max, sizeof(uint32_t) * capacity) == hipSuccess &&
-              hipMalloc(&p->d_rsv_max, sizeof(uint32_t) * capacity) == hipSuccess &&
-              hipMalloc(&p->d_pref, sizeof(uint64_t) * capacity) == hipSuccess &&
-              hipMalloc(&p->d_minors, sizeof(uint32_t) * (capacity + 1)) == hipSuccess &&
-              hipMalloc(&p->d_buckets, sizeof(uint64_t) * REPLAY_BUCKET_WORDS) == hipSuccess &&
-              hipMalloc(&p->d_aout, sizeof(int32_t) * 4) == hipSuccess &&
-              hipMalloc(&p->d_tkeys, sizeof(uint64_t) * KG_TOPK_MAX * capacity) == hipSuccess &&
-              hipMalloc(&p->d_spec, sizeof(uint32_t) * (2 * (size_t)capacity + DEV_CLASSES + 1)) == hipSuccess &&
-              hipMalloc(&p->d_pstat, sizeof(uint32_t) * capacity) == hipSuccess &&
-              hipMalloc(&p->d_reason, sizeof(uint32_t) * (capacity + 1)) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&p->in_copied, hipEventDisableTiming) == hipSuccess;
+    const size_t cap = capacity, keys = (size_t)KG_TOPK_MAX * cap;
+    const bool ok = !p->d_in.alloc(p->in_bytes) && !p->h_in.alloc(p->in_bytes) && !p->d_keys.alloc(keys) &&
+                    !p->h_keys.alloc(keys) && !p->d_winners.alloc(cap + 1) && !p->d_step.alloc(64) && !p->d_qst.alloc(cap) &&
+                    !p->d_dev_max.alloc(cap) && !p->d_rsv_max.alloc(cap) && !p->d_pref.alloc(cap) &&
+                    !p->d_minors.alloc(cap + 1) && !p->d_buckets.alloc(REPLAY_BUCKET_WORDS) && !p->d_aout.alloc(4) &&
+                    !p->d_tkeys.alloc(keys) && !p->d_spec.alloc(2 * cap + DEV_CLASSES + 1) && !p->d_pstat.alloc(cap) &&
+                    !p->d_reason.alloc(cap + 1) &&
+                    hipEventCreateWithFlags(&p->in_copied, hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         if (p->in_copied) hipEventDestroy(p->in_copied);
-        for (void* b : {(void*)p->d_in, (void*)p->d_keys, (void*)p->d_winners, (void*)p->d_step, (void*)p->d_qst,
-                        (void*)p->d_dev_max, (void*)p->d_rsv_max, (void*)p->d_pref, (void*)p->d_minors, (void*)p->d_buckets,
-                        (void*)p->d_aout, (void*)p->d_tkeys, (void*)p->d_spec, (void*)p->d_pstat, (void*)p->d_reason})
-            hipFree(b);
-        hipHostFree(p->h_in);
-        hipHostFree(p->h_keys);
         delete p;
         return fail(ctx, KG_OOM, "pod batch of %u", capacity);
     }
@@ -1766,9 +1704,9 @@ static kg_status derive_lanes(kg_pods* p, const int32_t* set) {
     }
     bool any = false;
     for (uint32_t j = 0; set && j < n; j++) any |= set[j] >= 0;
-    if (any && !p->d_sorder) {
-        HIP_TRY(ctx, hipMalloc(&p->d_sorder, sizeof(uint32_t) * p->cap));
-        HIP_TRY(ctx, hipMalloc(&p->d_srorder, sizeof(uint32_t) * p->cap));
+    if (any) {
+        HIP_TRY(ctx, p->d_sorder.reserve(p->cap));
+        HIP_TRY(ctx, p->d_srorder.reserve(p->cap));
     }
     const PodLayout L = pod_layout(n);
     uint8_t* h = p->h_in;
@@ -1858,20 +1796,10 @@ kg_status kg_pods_set_node_sets(kg_pods* p, const kg_node_sets* sets) {
     if (sets->n_nodes & 31u)
         for (uint32_t t = 0; t < sets->n_sets; t++) bits[(size_t)t * w32 + w32 - 1] &= (1u << (sets->n_nodes & 31u)) - 1u;
     const size_t tab_words = (size_t)sets->n_sets * sets_words(sets->n_nodes);
-    if (bits.size() > p->set_bits_cap || tab_words > p->set_tab_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        hipFree(p->d_set_bits);
-        hipFree(p->d_set_tab);
-        p->d_set_bits = nullptr;
-        p->d_set_tab = nullptr;
-        p->set_bits_cap = p->set_tab_cap = 0;
-        p->tab_valid = false;
-        HIP_TRY(ctx, hipMalloc(&p->d_set_bits, sizeof(uint32_t) * std::max<size_t>(bits.size(), 1)));
-        HIP_TRY(ctx, hipMalloc(&p->d_set_tab, sizeof(uint64_t) * std::max<size_t>(tab_words, 1)));
-        p->set_bits_cap = bits.size();
-        p->set_tab_cap = tab_words;
-    }
-    if (!p->d_pod_set) HIP_TRY(ctx, hipMalloc(&p->d_pod_set, sizeof(int32_t) * p->cap));
+    p->tab_valid = false;  // before a failure can leave d_set_tab empty
+    HIP_TRY(ctx, grow(ctx, p->d_set_bits, std::max<size_t>(bits.size(), 1)));
+    HIP_TRY(ctx, grow(ctx, p->d_set_tab, std::max<size_t>(tab_words, 1)));
+    HIP_TRY(ctx, p->d_pod_set.reserve(p->cap));
     if (n) HIP_TRY(ctx, hipMemcpyAsync(p->d_pod_set, ids.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
     if (!bits.empty())
         HIP_TRY(ctx, hipMemcpyAsync(p->d_set_bits, bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice,
@@ -1915,20 +1843,7 @@ kg_status kg_pods_destroy(kg_pods* p) {
     hipStreamSynchronize(p->ctx->stream);
     if (p->ctx->side) hipStreamSynchronize(p->ctx->side);  // a plain-pod select may still read the batch there
     if (p->ctx->side2) hipStreamSynchronize(p->ctx->side2);  // and a class-1 lane of the config-5 kernels
-    for (void* b : {(void*)p->d_ipairs, (void*)p->d_ipair_count, (void*)p->d_sacc, (void*)p->d_pod_set, (void*)p->d_sorder,
-                    (void*)p->d_srorder, (void*)p->d_set_bits, (void*)p->d_set_tab})
-        hipFree(b);
-    for (void* b : {(void*)p->d_in, (void*)p->d_keys, (void*)p->d_winners, (void*)p->d_step, (void*)p->d_partial,
-                    (void*)p->d_gather, (void*)p->d_qst, (void*)p->d_dev_max, (void*)p->d_rsv_max, (void*)p->d_pref,
-                    (void*)p->d_minors, (void*)p->d_buckets, (void*)p->d_aout, (void*)p->d_tkeys, (void*)p->d_pstat,
-                    (void*)p->d_reason, (void*)p->d_devsum, (void*)p->d_gz, (void*)p->d_spec, (void*)p->d_split, (void*)p->d_batch, (void*)p->d_rcode, (void*)p->d_done, (void*)p->d_rec, (void*)p->d_xpairs,
-                    (void*)p->d_diag_rows, (void*)p->d_diag})
-        hipFree(b);
-    hipHostFree(p->h_in);
-    hipHostFree(p->h_keys);
     if (p->in_copied) hipEventDestroy(p->in_copied);
-    hipFree(p->d_rbpart);
-    hipFree(p->d_rbtops);
     if (p->rexec) hipGraphExecDestroy(p->rexec);
     if (p->xexec) hipGraphExecDestroy(p->xexec);
     if (p->bexec) hipGraphExecDestroy(p->bexec);
@@ -1958,10 +1873,9 @@ static kg_status ext_verify(kg_snap* s, kg_pods* p, kg_verify_out* out) {
     if (pairs == 0) return KG_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ExtVerifyDev d{};
-    void* buf = nullptr;
-    HIP_TRY(ctx, hipMalloc(&buf, pairs * (4 + 8 * 7 + 1)));
-    char* b = (char*)buf;
-    d.s_nrf = (int64_t*)b;
+    DevBuf<uint8_t> buf;  // freed on return: after the final synchronisation on the success path
+    HIP_TRY(ctx, buf.alloc(pairs * (4 + 8 * 7 + 1)));
+    d.s_nrf = reinterpret_cast<int64_t*>(buf.get());
     d.s_la = d.s_nrf + pairs;
     d.s_numa = d.s_la + pairs;
     d.s_dev = d.s_numa + pairs;
@@ -1971,24 +1885,19 @@ static kg_status ext_verify(kg_snap* s, kg_pods* p, kg_verify_out* out) {
     d.status = (uint32_t*)(d.total + pairs);
     d.zone = (int8_t*)(d.status + pairs);
     const ExtDev e = s->ext_dev();
-    hipError_t err = launch_ext_gate(p->dev, p->n, e, s->cfg.plugins, p->d_qst, nullptr, ctx->stream);
-    if (err == hipSuccess)
-        err = launch_ext_verify(s->d_nodes, s->d_zones, e, p->dev, p->n, s->n, s->base, s->kcfg, force_exact(), p->d_qst,
-                                d, ctx->stream);
-    if (err == hipSuccess) {
-        struct {
-            void* dst;
-            const void* src;
-            size_t sz;
-        } cp[] = {{out->status, d.status, 4},     {out->score_nrf, d.s_nrf, 8}, {out->score_la, d.s_la, 8},
-                  {out->score_numa, d.s_numa, 8}, {out->total, d.total, 8},     {out->numa_zone, d.zone, 1},
-                  {out->score_dev, d.s_dev, 8},   {out->score_rsv, d.s_rsv, 8}};
-        for (auto& c : cp)
-            if (c.dst && err == hipSuccess) err = hipMemcpyAsync(c.dst, c.src, c.sz * pairs, hipMemcpyDeviceToHost, ctx->stream);
-        if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    }
-    hipFree(buf);
-    HIP_TRY(ctx, err);
+    HIP_TRY(ctx, launch_ext_gate(p->dev, p->n, e, s->cfg.plugins, p->d_qst, nullptr, ctx->stream));
+    HIP_TRY(ctx, launch_ext_verify(s->d_nodes, s->d_zones, e, p->dev, p->n, s->n, s->base, s->kcfg, force_exact(), p->d_qst, d,
+                                   ctx->stream));
+    struct {
+        void* dst;
+        const void* src;
+        size_t sz;
+    } cp[] = {{out->status, d.status, 4},     {out->score_nrf, d.s_nrf, 8}, {out->score_la, d.s_la, 8},
+              {out->score_numa, d.s_numa, 8}, {out->total, d.total, 8},     {out->numa_zone, d.zone, 1},
+              {out->score_dev, d.s_dev, 8},   {out->score_rsv, d.s_rsv, 8}};
+    for (auto& c : cp)
+        if (c.dst) HIP_TRY(ctx, hipMemcpyAsync(c.dst, c.src, c.sz * pairs, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return KG_OK;
 }
 
@@ -2010,34 +1919,28 @@ kg_status kg_eval_verify(kg_snap* s, kg_pods* p, kg_verify_out* out) {
     if (pairs == 0) return KG_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     VerifyDev d{};
-    void* buf = nullptr;
-    const size_t bytes = pairs * (4 + 8 * 4 + 1);
-    HIP_TRY(ctx, hipMalloc(&buf, bytes));
-    char* b = (char*)buf;
-    d.s_nrf = (int64_t*)b;
+    DevBuf<uint8_t> buf;  // freed on return: after the final synchronisation on the success path
+    HIP_TRY(ctx, buf.alloc(pairs * (4 + 8 * 4 + 1)));
+    d.s_nrf = reinterpret_cast<int64_t*>(buf.get());
     d.s_la = d.s_nrf + pairs;
     d.s_numa = d.s_la + pairs;
     d.total = d.s_numa + pairs;
     d.status = (uint32_t*)(d.total + pairs);
     d.zone = (int8_t*)(d.status + pairs);
-    hipError_t e = launch_verify(s->d_nodes, s->d_zones, p->dev, p->n, s->n, s->kcfg, force_exact(), d, ctx->stream);
+    HIP_TRY(ctx, launch_verify(s->d_nodes, s->d_zones, p->dev, p->n, s->n, s->kcfg, force_exact(), d, ctx->stream));
     // excluded pairs: the output matrix is in snapshot order, like the uploaded bitmap
-    if (e == hipSuccess && p->any_set) e = launch_sets_verify(p->sets_dev(), p->n, s->n, d.status, d.total, ctx->stream);
-    if (e == hipSuccess) {
-        struct {
-            void* dst;
-            const void* src;
-            size_t sz;
-        } cp[] = {{out->status, d.status, 4}, {out->score_nrf, d.s_nrf, 8}, {out->score_la, d.s_la, 8},
-                  {out->score_numa, d.s_numa, 8}, {out->total, d.total, 8}, {out->numa_zone, d.zone, 1}};
-        for (auto& c : cp)
-            if (c.dst && e == hipSuccess) e = hipMemcpyAsync(c.dst, c.src, c.sz * pairs, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    }
-    if (e == hipSuccess && out->score_dev) std::memset(out->score_dev, 0, 8 * pairs);
-    if (e == hipSuccess && out->score_rsv) std::memset(out->score_rsv, 0, 8 * pairs);
-    hipFree(buf);
-    HIP_TRY(ctx, e);
+    if (p->any_set) HIP_TRY(ctx, launch_sets_verify(p->sets_dev(), p->n, s->n, d.status, d.total, ctx->stream));
+    struct {
+        void* dst;
+        const void* src;
+        size_t sz;
+    } cp[] = {{out->status, d.status, 4}, {out->score_nrf, d.s_nrf, 8}, {out->score_la, d.s_la, 8},
+              {out->score_numa, d.s_numa, 8}, {out->total, d.total, 8}, {out->numa_zone, d.zone, 1}};
+    for (auto& c : cp)
+        if (c.dst) HIP_TRY(ctx, hipMemcpyAsync(c.dst, c.src, c.sz * pairs, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (out->score_dev) std::memset(out->score_dev, 0, 8 * pairs);
+    if (out->score_rsv) std::memset(out->score_rsv, 0, 8 * pairs);
     return KG_OK;
 }
 
@@ -2045,16 +1948,10 @@ kg_status kg_eval_verify(kg_snap* s, kg_pods* p, kg_verify_out* out) {
 static kg_status ensure_diag(kg_pods* p, size_t n_rows) {
     kg_ctx* ctx = p->ctx;
     if (n_rows <= p->diag_cap) return KG_OK;
-    if (p->d_diag || p->d_diag_rows) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        hipFree(p->d_diag);
-        hipFree(p->d_diag_rows);
-        p->d_diag = p->d_diag_rows = nullptr;
-        p->diag_cap = 0;
-    }
+    p->diag_cap = 0;
     const size_t cap = std::max<size_t>(n_rows, 64);
-    HIP_TRY(ctx, hipMalloc(&p->d_diag, sizeof(uint32_t) * KG_DIAG_SLOTS * cap));
-    HIP_TRY(ctx, hipMalloc(&p->d_diag_rows, sizeof(uint32_t) * cap));
+    HIP_TRY(ctx, grow(ctx, p->d_diag, KG_DIAG_SLOTS * cap));
+    HIP_TRY(ctx, grow(ctx, p->d_diag_rows, cap));
     p->diag_cap = cap;
     return KG_OK;
 }
@@ -2105,19 +2002,6 @@ kg_status kg_eval_diagnose(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_
     return KG_OK;
 }
 
-static kg_status ensure_partial(kg_pods* p, size_t need) {
-    kg_ctx* ctx = p->ctx;
-    if (need <= p->partial_cap) return KG_OK;
-    if (p->d_partial) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipFree(p->d_partial));
-        p->d_partial = nullptr;
-    }
-    HIP_TRY(ctx, hipMalloc(&p->d_partial, sizeof(uint64_t) * need));
-    p->partial_cap = need;
-    return KG_OK;
-}
-
 // config-5 pass 1 / pass 2 take the base plugins from the fast block where the fast path is valid:
 // same conditions as the plain-pod split, plus all three base plugins enabled (eval_fast_key<7>)
 static bool ext_fast_base(const kg_snap* s, const kg_pods* p) {
@@ -2162,28 +2046,13 @@ static uint32_t live_est(const kg_snap* s, const kg_pods* p) {
 
 // room for the batch's DevSum table over this snapshot's records
 static kg_status devsum_reserve(kg_snap* s, kg_pods* p) {
-    kg_ctx* ctx = s->ctx;
-    if (p->devsum_cap >= s->n) return KG_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipFree(p->d_devsum));
-    p->d_devsum = nullptr;
-    p->devsum_cap = 0;
-    HIP_TRY(ctx, hipMalloc(&p->d_devsum, sizeof(DevSum) * std::max<uint32_t>(s->n, 1)));
-    p->devsum_cap = s->n;
+    HIP_TRY(s->ctx, grow(s->ctx, p->d_devsum, s->n));
     return KG_OK;
 }
 
 // room for the batch's e.gz table (gpu_zone_sum per SingleNUMANode record and GPU request class)
 static kg_status gz_reserve(kg_snap* s, kg_pods* p) {
-    kg_ctx* ctx = s->ctx;
-    const size_t need = (size_t)(s->n - s->n0) * DEV_CLASSES;
-    if (p->gz_cap >= need) return KG_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipFree(p->d_gz));
-    p->d_gz = nullptr;
-    p->gz_cap = 0;
-    HIP_TRY(ctx, hipMalloc(&p->d_gz, sizeof(uint64_t) * std::max<size_t>(need, 1)));
-    p->gz_cap = need;
+    HIP_TRY(s->ctx, grow(s->ctx, p->d_gz, (size_t)(s->n - s->n0) * DEV_CLASSES));
     return KG_OK;
 }
 
@@ -2219,15 +2088,7 @@ static kg_status ext_dev_sum(kg_snap* s, kg_pods* p, ExtDev& e, bool* lane_open)
         if (gst != KG_OK) return gst;
     }
     const bool codes = s->n_rdev && s->d_rdev && p->n_dclass;
-    if (codes && p->rcode_cap < (size_t)s->n_rdev * DEV_CLASSES) {
-        const size_t need = (size_t)s->n_rdev * DEV_CLASSES;
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipFree(p->d_rcode));
-        p->d_rcode = nullptr;
-        p->rcode_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&p->d_rcode, need));
-        p->rcode_cap = need;
-    }
+    if (codes) HIP_TRY(ctx, grow(ctx, p->d_rcode, (size_t)s->n_rdev * DEV_CLASSES));
     // DeviceShare's NUMA hints of the SingleNUMANode records (per class) on the second side lane beside DevSum and
     // the restore tables' codes: the three tables are independent. DevSum is submitted first (the accumulators and its
     // cls_max were zeroed before the quota gate, ext_gate_local): the statistics wait for it.
@@ -2311,7 +2172,7 @@ static kg_status ext_stats_local(kg_snap* s, kg_pods* p, bool gated = false) {
     dst = ext_dev_sum(s, p, e, &zone_lane);
     if (dst != KG_OK) return dst;
     if (ext_fast_base(s, p)) {  // records for the PART 2 kernels (pass 1 and pass 2 of this batch)
-        if (!s->d_special) HIP_TRY(ctx, hipMalloc(&s->d_special, sizeof(uint32_t) * 2 * ((size_t)s->n + 1)));
+        HIP_TRY(ctx, s->d_special.reserve(2 * ((size_t)s->n + 1)));
         HIP_TRY(ctx, launch_special_scan(s->d_nodes, s->n, s->n0, s->d_special, const_cast<uint32_t*>(c1_list(s, p)),
                                          ctx->stream));
     }
@@ -2326,19 +2187,8 @@ static kg_status ext_stats_local(kg_snap* s, kg_pods* p, bool gated = false) {
         const uint32_t xn = split ? p->n_x : p->n;
         const size_t need = (size_t)xn * (T + 1);
         if (need * sizeof(uint64_t) <= ((size_t)4 << 30)) {
-            if (p->xpairs_cap < need) {
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                HIP_TRY(ctx, hipFree(p->d_xpairs));
-                p->d_xpairs = nullptr;
-                p->xpairs_cap = 0;
-                // the stored pairs are a speed-up only: without the memory the select evaluates those pairs again
-                if (hipMalloc(&p->d_xpairs, sizeof(uint64_t) * std::max<size_t>(need, 1)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    p->d_xpairs = nullptr;
-                } else {
-                    p->xpairs_cap = need;
-                }
-            }
+            // the stored pairs are a speed-up only: without the memory the select evaluates those pairs again
+            if (grow(ctx, p->d_xpairs, need) != hipSuccess) (void)hipGetLastError();
             if (p->d_xpairs) {
                 HIP_TRY(ctx, hipMemsetAsync(p->d_xpairs + (size_t)T * xn, 0, sizeof(uint64_t) * xn, ctx->stream));
                 p->xT = T;
@@ -2539,8 +2389,7 @@ static kg_status ext_select_local(kg_snap* s, kg_pods* p, uint32_t kk, uint64_t*
     uint32_t fparts = 0;
     LaunchSelect a = make_select(s, p->dev, p->d_pmap, n_plain, n_plain, p->n, kk, true, d_out, nullptr, p->d_pstat, &fparts);
     const size_t xneed = (size_t)xparts * n_x * kk;
-    kg_status st = ensure_partial(p, std::max<size_t>(xneed + (size_t)fparts * p->n * kk, 1));
-    if (st != KG_OK) return st;
+    HIP_TRY(ctx, grow(ctx, p->d_partial, std::max<size_t>(xneed + (size_t)fparts * p->n * kk, 1)));
     a.partial = p->d_partial + xneed;
     uint64_t* xkeys = split ? p->d_tkeys : d_out;            // the x rows' merged keys
     uint64_t* xpart = fused ? xkeys : p->d_partial;          // where the x kernels write
@@ -2755,14 +2604,12 @@ static kg_status ensure_prof(kg_ctx* ctx, uint64_t** out) {
     }
     if (ctx->clock_khz == 0) return KG_OK;
     if (!ctx->d_prof) {
-        uint64_t* d = nullptr;
-        HIP_TRY(ctx, hipMalloc(&d, 2 * sizeof(uint64_t)));
-        const hipError_t e = hipMemsetAsync(d, 0, 2 * sizeof(uint64_t), ctx->stream);
+        HIP_TRY(ctx, ctx->d_prof.alloc(2));
+        const hipError_t e = hipMemsetAsync(ctx->d_prof, 0, 2 * sizeof(uint64_t), ctx->stream);
         if (e != hipSuccess) {
-            hipFree(d);
+            ctx->d_prof.reset();
             HIP_TRY(ctx, e);
         }
-        ctx->d_prof = d;
         ctx->prof_seen[0] = ctx->prof_seen[1] = 0;
         ctx->prof_pending = 0;
     }
@@ -2795,19 +2642,12 @@ static kg_status small_phases_write(kg_ctx* ctx, const char* file, uint32_t nc) 
 static kg_status ensure_sacc(kg_pods* p, uint32_t replicas, uint32_t lp) {
     kg_ctx* ctx = p->ctx;
     const size_t need = SACC_HEAD + (size_t)replicas * lp * 16;
-    if (need > p->sacc_cap) {
-        if (p->d_sacc) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipFree(p->d_sacc));
-            p->d_sacc = nullptr;
-            p->sacc_cap = 0;
-        }
-        HIP_TRY(ctx, hipMalloc(&p->d_sacc, need));
-        p->sacc_cap = need;
+    if (need > p->d_sacc.cap()) {
+        HIP_TRY(ctx, grow(ctx, p->d_sacc, need));
         p->sacc_dirty = true;
     }
     if (p->sacc_dirty) {
-        HIP_TRY(ctx, hipMemsetAsync(p->d_sacc, 0, p->sacc_cap, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(p->d_sacc, 0, p->d_sacc.cap(), ctx->stream));
         p->sacc_dirty = false;
     }
     return KG_OK;
@@ -2890,14 +2730,13 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
             st = ensure_sacc(p, a.small_replicas, lp);
             if (st != KG_OK) return st;
             const size_t slots = (size_t)a.small_replicas * lp;
-            a.sticket = reinterpret_cast<uint32_t*>(p->d_sacc);
+            a.sticket = reinterpret_cast<uint32_t*>(p->d_sacc.get());
             a.skeys = reinterpret_cast<uint64_t*>(p->d_sacc + SACC_HEAD);
             a.sfhi = reinterpret_cast<uint32_t*>(a.skeys + slots);
             a.sub = a.sfhi + slots;
         } else {
             const size_t slots = (size_t)(a.range[0].n_chunks + a.range[1].n_chunks) * lp;
-            st = ensure_partial(p, 2 * slots);
-            if (st != KG_OK) return st;
+            HIP_TRY(ctx, grow(ctx, p->d_partial, 2 * slots));
             a.skeys = p->d_partial;
             a.sub = reinterpret_cast<uint32_t*>(p->d_partial + slots);
             a.sfhi = a.sub + slots;
@@ -2913,14 +2752,7 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         const char* phases = small_phases_file(a, lp);
         st = KG_OK;
         if (phases) {  // a launch of the measurement aid has no bracket: its tick pair is the scratch one in d_phases
-            if (ctx->phases_cap < (size_t)nc * 4 + 2) {
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                if (ctx->d_phases) hipFree(ctx->d_phases);
-                ctx->d_phases = nullptr;
-                ctx->phases_cap = 0;
-                HIP_TRY(ctx, hipMalloc(&ctx->d_phases, sizeof(uint64_t) * ((size_t)nc * 4 + 2)));
-                ctx->phases_cap = (size_t)nc * 4 + 2;
-            }
+            HIP_TRY(ctx, grow(ctx, ctx->d_phases, (size_t)nc * 4 + 2));
             a.phases = true;
             a.prof = ctx->d_phases;
         } else if (ctx->profiling && a.small_replicas && !std::getenv("KG_PROFILE_BOUND_EVENTS")) {
@@ -2947,8 +2779,8 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     HIP_TRY(ctx, hipMemsetAsync(p->d_pstat, 0, sizeof(uint32_t) * p->n, ctx->stream));
     // the set lanes insert into zeroed rows by atomics, whichever form the other lanes' launch takes
     if (p->any_set) HIP_TRY(ctx, hipMemsetAsync(d_out, 0, sizeof(uint64_t) * kk * p->n, ctx->stream));
-    kg_status st = ensure_partial(p, std::max<size_t>((size_t)parts * p->n * kk, 1));
-    if (st != KG_OK) return st;
+    HIP_TRY(ctx, grow(ctx, p->d_partial, std::max<size_t>((size_t)parts * p->n * kk, 1)));
+    kg_status st = KG_OK;
     a.partial = p->d_partial;
     const uint32_t n_int = a.n_pods - a.n_fast;
     if (n_int && !a.exact && s->weights_small && (kk == 1 || a.fused_k) && !std::getenv("KG_NO_IPRUNE")) {
@@ -2956,14 +2788,9 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         // a launch that needs more than 2^26 slots keeps the unpruned kernel
         const size_t cap = std::min<size_t>((size_t)(n_int + 255) / 256 * 256 * ((size_t)s->n + 4096), (size_t)1 << 26);
         if (p->ipairs_cap < cap) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            hipFree(p->d_ipairs);
-            hipFree(p->d_ipair_count);
-            p->d_ipairs = nullptr;
-            p->d_ipair_count = nullptr;
             p->ipairs_cap = 0;
-            HIP_TRY(ctx, hipMalloc(&p->d_ipairs, sizeof(uint64_t) * cap));
-            HIP_TRY(ctx, hipMalloc(&p->d_ipair_count, sizeof(uint32_t) * (cap / (256 * 64) + 1)));
+            HIP_TRY(ctx, grow(ctx, p->d_ipairs, cap));
+            HIP_TRY(ctx, grow(ctx, p->d_ipair_count, cap / (256 * 64) + 1));
             p->ipairs_cap = cap;
         }
         a.ipairs = p->d_ipairs;
@@ -3098,10 +2925,11 @@ bool cpuset_active(const kg_snap* s, const kg_pods* p) {
 std::vector<uint8_t> replay_key(const kg_snap* s, const kg_pods* p, bool exact, bool reasons = false) {
     std::vector<uint8_t> k;
     auto put = [&k](const void* x, size_t n) { k.insert(k.end(), (const uint8_t*)x, (const uint8_t*)x + n); };
+    auto putp = [&put](const void* d) { put(&d, sizeof(d)); };  // a buffer's address
     put(&reasons, sizeof(reasons));
-    put(&s->d_nodes, sizeof(s->d_nodes));
-    put(&s->d_zones, sizeof(s->d_zones));
-    put(&s->d_zsel, sizeof(s->d_zsel));
+    putp(s->d_nodes);
+    putp(s->d_zones);
+    putp(s->d_zsel);
     put(&s->n, sizeof(s->n));
     put(&s->base, sizeof(s->base));
     put(&s->kcfg, sizeof(s->kcfg));
@@ -3109,9 +2937,9 @@ std::vector<uint8_t> replay_key(const kg_snap* s, const kg_pods* p, bool exact, 
     put(&exact, sizeof(exact));
     const bool cs = cpuset_active(s, p);
     put(&cs, sizeof(cs));
-    put(&s->d_cpu_alloc, sizeof(s->d_cpu_alloc));
-    put(&s->d_cpu_topos, sizeof(s->d_cpu_topos));
-    put(&s->d_pos, sizeof(s->d_pos));
+    putp(s->d_cpu_alloc);
+    putp(s->d_cpu_topos);
+    putp(s->d_pos);
     // a batch with candidate node sets replays through other kernel instantiations, over its own tables
     const int32_t* ps = p->any_set ? p->d_pod_set : nullptr;
     const uint64_t* tab = p->any_set ? p->d_set_tab : nullptr;
@@ -3204,25 +3032,19 @@ kg_status rb_graph(kg_snap* s, kg_pods* p, bool exact) {
     a.step = p->d_step;
     a.winners = p->d_winners;
     const size_t need = (size_t)std::max<uint32_t>(n_parts, 1) * RB_W * RB_K;
-    if (p->rbpart_cap < need) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        hipFree(p->d_rbpart);
-        p->d_rbpart = nullptr;
-        p->rbpart_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&p->d_rbpart, sizeof(uint64_t) * need));
-        p->rbpart_cap = need;
-    }
-    if (!p->d_rbtops) HIP_TRY(ctx, hipMalloc(&p->d_rbtops, sizeof(uint64_t) * RB_W * RB_K));
+    HIP_TRY(ctx, grow(ctx, p->d_rbpart, need));
+    HIP_TRY(ctx, p->d_rbtops.reserve((size_t)RB_W * RB_K));
     a.partial = p->d_rbpart;
     a.tops = p->d_rbtops;
     p->rb_args = a;
     std::vector<uint8_t> key = replay_key(s, p, exact);
     auto put = [&key](const void* x, size_t n) { key.insert(key.end(), (const uint8_t*)x, (const uint8_t*)x + n); };
-    put(&s->d_pos, sizeof(s->d_pos));
+    auto putp = [&put](const void* d) { put(&d, sizeof(d)); };  // a buffer's address
+    putp(s->d_pos);
     put(&s->n0, sizeof(s->n0));
     put(&a.fast, sizeof(a.fast));
-    put(&p->d_rbpart, sizeof(p->d_rbpart));
-    put(&p->d_rbtops, sizeof(p->d_rbtops));
+    putp(p->d_rbpart);
+    putp(p->d_rbtops);
     if (p->bexec && key == p->bkey) return KG_OK;
     if (p->bexec) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -3250,6 +3072,7 @@ kg_status ext_replay_graph(kg_snap* s, kg_pods* p, bool exact, bool reasons) {
     kg_ctx* ctx = s->ctx;
     std::vector<uint8_t> key = replay_key(s, p, exact, reasons);
     auto put = [&key](const void* x, size_t n) { key.insert(key.end(), (const uint8_t*)x, (const uint8_t*)x + n); };
+    auto putp = [&put](const void* d) { put(&d, sizeof(d)); };  // a buffer's address
     // every ExtDev field the captured launches take by value (tables re-uploaded in place keep their pointers)
     ExtDev e = s->ext_dev();
     e.dsum = replay_dsum(s, p) ? p->d_devsum : nullptr;
@@ -3278,13 +3101,13 @@ kg_status ext_replay_graph(kg_snap* s, kg_pods* p, bool exact, bool reasons) {
     put(&e.binpack, sizeof(e.binpack));
     RsvStep* rs = rsv_replay(s) ? s->d_rstep : nullptr;
     put(&rs, sizeof(rs));
-    put(&s->d_rlist, sizeof(s->d_rlist));
+    putp(s->d_rlist);
     const bool cs = cpuset_active(s, p);
     put(&cs, sizeof(cs));
-    put(&s->d_cpu_alloc, sizeof(s->d_cpu_alloc));
-    put(&s->d_cpu_topos, sizeof(s->d_cpu_topos));
-    put(&s->d_pos, sizeof(s->d_pos));
-    put(&p->d_done, sizeof(p->d_done));
+    putp(s->d_cpu_alloc);
+    putp(s->d_cpu_topos);
+    putp(s->d_pos);
+    putp(p->d_done);
     if (p->xexec && key == p->xkey) return KG_OK;
     if (p->xexec) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -3401,7 +3224,7 @@ static kg_status assume_impl(kg_snap* s, kg_pods* p, uint32_t pod, uint32_t node
     if (rsv_numa_pair(s, p, pod, node))
         return fail(ctx, KG_UNSUPPORTED, "pod %u on node %u: NUMA / cpuset restore of its reservations", pod, node);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (out_split && !p->d_split) HIP_TRY(ctx, hipMalloc(&p->d_split, sizeof(int64_t) * 2 * KG_MAX_ZONES));
+    if (out_split) HIP_TRY(ctx, p->d_split.reserve(2 * KG_MAX_ZONES));
     touch_views(s, node);
     HIP_TRY(ctx, hipMemsetAsync(p->d_aout, 0, sizeof(int32_t) * 2, ctx->stream));
     if (out_split) HIP_TRY(ctx, hipMemsetAsync(p->d_split, 0, sizeof(int64_t) * 2 * KG_MAX_ZONES, ctx->stream));
@@ -3444,7 +3267,7 @@ static kg_status forget_impl(kg_snap* s, kg_pods* p, uint32_t pod, uint32_t node
                                          "amounts (kg_forget_numa)", zone);
     if (cpuset_bound(s, p, pod, node)) return fail(ctx, KG_UNSUPPORTED, "Unreserve of a cpuset allocation");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (multi && !p->d_split) HIP_TRY(ctx, hipMalloc(&p->d_split, sizeof(int64_t) * 2 * KG_MAX_ZONES));
+    if (multi) HIP_TRY(ctx, p->d_split.reserve(2 * KG_MAX_ZONES));
     touch_views(s, node);
     if (multi)
         HIP_TRY(ctx, hipMemcpyAsync(p->d_split, split, sizeof(int64_t) * 2 * KG_MAX_ZONES, hipMemcpyHostToDevice, ctx->stream));
@@ -3475,11 +3298,11 @@ static kg_status ext_replay(kg_snap* s, kg_pods* p, int32_t* out_node, int64_t* 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint32_t n = p->n;
     const bool exact = force_exact();
-    if (rsv_replay(s) && !s->d_rstep) {
-        HIP_TRY(ctx, hipMalloc(&s->d_rstep, sizeof(RsvStep) * 3));
-        HIP_TRY(ctx, hipMalloc(&s->d_rlist, sizeof(uint64_t) * 2 * 3 * (size_t)std::max<uint32_t>(s->n, 1)));
+    if (rsv_replay(s)) {
+        HIP_TRY(ctx, s->d_rstep.reserve(3));
+        HIP_TRY(ctx, s->d_rlist.reserve(2 * 3 * (size_t)std::max<uint32_t>(s->n, 1)));
     }
-    if (!p->d_done) HIP_TRY(ctx, hipMalloc(&p->d_done, REPLAY_DONE_WORDS * sizeof(uint32_t)));
+    HIP_TRY(ctx, p->d_done.reserve(REPLAY_DONE_WORDS));
     HIP_TRY(ctx, hipMemsetAsync(p->d_done, 0, REPLAY_DONE_WORDS * sizeof(uint32_t), ctx->stream));
     const bool reasons = out_reason != nullptr;
     if (replay_dsum(s, p)) {
@@ -3615,7 +3438,7 @@ kg_status kg_reserve(kg_snap* s, kg_pods* p, uint32_t pod, uint32_t node, kg_res
         if (st != KG_OK) return st;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!p->d_rec) HIP_TRY(ctx, hipMalloc(&p->d_rec, sizeof(uint64_t) * 16));
+    HIP_TRY(ctx, p->d_rec.reserve(16));
     // Reservation.Reserve follows the node's views on the device unless a reservation there holds GPUs (their DeviceShare
     // restore tables follow the reserve pods' allocations: the caller re-uploads the node's views)
     const bool rsv = (s->cfg.plugins & KG_PLUGIN_RSV) && s->n_views && s->rsv_follow();
@@ -3670,7 +3493,7 @@ kg_status kg_unreserve(kg_snap* s, kg_pods* p, uint32_t pod, uint32_t node, kg_r
         if (st != KG_OK) return st;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!p->d_rec) HIP_TRY(ctx, hipMalloc(&p->d_rec, sizeof(uint64_t) * 16));
+    HIP_TRY(ctx, p->d_rec.reserve(16));
     const bool rsv = (s->cfg.plugins & KG_PLUGIN_RSV) && s->n_views && s->rsv_follow();
     if (!rsv) touch_views(s, node);
     else if (node < s->cls_mask.size() && s->cls_mask[node]) s->views_on_device = true;
@@ -3726,9 +3549,8 @@ kg_status kg_cpuset_take(kg_ctx* ctx, const kg_cpu_topo* topos, uint32_t n_topos
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t bt = sizeof(kg_cpu_topo) * n_topos, ba = sizeof(kg_cpu_alloc) * (allocs ? n_allocs : 0),
                  bq = sizeof(kg_cpuset_request) * n, bo = sizeof(uint64_t) * 4 * n, br = sizeof(int32_t) * n;
-    uint8_t* d = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d, bt + ba + bq + bo + br + 64));
-    kg_status st = KG_OK;
+    DevBuf<uint8_t> d;  // freed on return: after the final synchronisation on the success path
+    HIP_TRY(ctx, d.alloc(bt + ba + bq + bo + br + 64));
     uint8_t* p = d;
     auto* d_topo = reinterpret_cast<kg_cpu_topo*>(p);
     p += bt;
@@ -3740,16 +3562,14 @@ kg_status kg_cpuset_take(kg_ctx* ctx, const kg_cpu_topo* topos, uint32_t n_topos
     auto* d_out = reinterpret_cast<uint64_t*>(p);
     p += bo;
     auto* d_rc = reinterpret_cast<int32_t*>(p);
-    hipError_t e = hipMemcpyAsync(d_topo, topos, bt, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && ba) e = hipMemcpyAsync(d_alloc, allocs, ba, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_req, reqs, bq, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = launch_cpuset_take(d_topo, d_alloc, d_req, n, d_out, d_rc, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bo, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(rc, d_rc, br, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) st = fail(ctx, KG_DEVICE_ERROR, "kg_cpuset_take: %s", hipGetErrorString(e));
-    hipFree(d);
-    return st;
+    HIP_TRY(ctx, hipMemcpyAsync(d_topo, topos, bt, hipMemcpyHostToDevice, ctx->stream));
+    if (ba) HIP_TRY(ctx, hipMemcpyAsync(d_alloc, allocs, ba, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_req, reqs, bq, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, launch_cpuset_take(d_topo, d_alloc, d_req, n, d_out, d_rc, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, bo, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(rc, d_rc, br, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KG_OK;
 }
 
 // ---- checkpoint / rollback and the inline batch cycle ------------------------------------------------
@@ -3757,17 +3577,11 @@ kg_status kg_cpuset_take(kg_ctx* ctx, const kg_cpu_topo* topos, uint32_t n_topos
 static kg_status save_state(kg_snap* s, kg_snap::Saved& k) {
     kg_ctx* ctx = s->ctx;
     const size_t n = std::max<uint32_t>(s->n, 1);
-    if (!k.nodes) {
-        HIP_TRY(ctx, hipMalloc(&k.nodes, sizeof(NodeRec) * n));
-        HIP_TRY(ctx, hipMalloc(&k.zones, sizeof(ZoneRec) * n));
-        if (s->d_dev) HIP_TRY(ctx, hipMalloc(&k.dev, sizeof(DevRec) * n));
-    }
-    if (s->d_cpu_alloc && !k.cpu) HIP_TRY(ctx, hipMalloc(&k.cpu, sizeof(kg_cpu_alloc) * n));
-    if (k.nq < s->n_quotas || (s->n_quotas && !k.q)) {
-        hipFree(k.q);
-        k.q = nullptr;
-        HIP_TRY(ctx, hipMalloc(&k.q, sizeof(QuotaState) * 2 * (size_t)s->n_quotas));
-    }
+    HIP_TRY(ctx, k.nodes.reserve(n));
+    HIP_TRY(ctx, k.zones.reserve(n));
+    if (s->d_dev) HIP_TRY(ctx, k.dev.reserve(n));
+    if (s->d_cpu_alloc) HIP_TRY(ctx, k.cpu.reserve(n));
+    HIP_TRY(ctx, grow(ctx, k.q, 2 * (size_t)s->n_quotas));
     k.nq = s->n_quotas;
     HIP_TRY(ctx, hipMemcpyAsync(k.nodes, s->d_nodes, sizeof(NodeRec) * s->n, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(k.zones, s->d_zones, sizeof(ZoneRec) * s->n, hipMemcpyDeviceToDevice, ctx->stream));
@@ -3778,13 +3592,9 @@ static kg_status save_state(kg_snap* s, kg_snap::Saved& k) {
         HIP_TRY(ctx, hipMemcpyAsync(k.q, s->d_qstate, sizeof(QuotaState) * 2 * (size_t)s->n_quotas, hipMemcpyDeviceToDevice,
                                     ctx->stream));
     const uint32_t ni = (uint32_t)s->h_infos.size();
-    if (s->n_views && (k.nv < s->n_views || k.ni < ni || !k.views)) {
-        hipFree(k.views);
-        hipFree(k.infos);
-        k.views = nullptr;
-        k.infos = nullptr;
-        HIP_TRY(ctx, hipMalloc(&k.views, sizeof(RsvView) * s->n_views));
-        HIP_TRY(ctx, hipMalloc(&k.infos, sizeof(RsvInfo) * std::max<uint32_t>(ni, 1)));
+    if (s->n_views) {
+        HIP_TRY(ctx, grow(ctx, k.views, s->n_views));
+        HIP_TRY(ctx, grow(ctx, k.infos, std::max<uint32_t>(ni, 1)));
     }
     k.nv = s->n_views;
     k.ni = ni;
@@ -3793,13 +3603,9 @@ static kg_status save_state(kg_snap* s, kg_snap::Saved& k) {
         if (ni) HIP_TRY(ctx, hipMemcpyAsync(k.infos, s->d_infos, sizeof(RsvInfo) * ni, hipMemcpyDeviceToDevice, ctx->stream));
     }
     if (s->gpu_raw) {  // the GPU restore tables and inputs a Reserve rebuilds
-        if (k.nrd < s->n_rdev || k.ngn < s->n_gnodes || k.ngr < s->n_grsv || !k.rdev) {
-            for (void* b : {(void*)k.rdev, (void*)k.gnodes, (void*)k.grsv}) hipFree(b);
-            k.rdev = nullptr, k.gnodes = nullptr, k.grsv = nullptr;
-            HIP_TRY(ctx, hipMalloc(&k.rdev, sizeof(DevRec) * std::max<uint32_t>(s->n_rdev, 1)));
-            HIP_TRY(ctx, hipMalloc(&k.gnodes, sizeof(GpuRawNode) * std::max<uint32_t>(s->n_gnodes, 1)));
-            HIP_TRY(ctx, hipMalloc(&k.grsv, sizeof(GpuRawRsv) * std::max<uint32_t>(s->n_grsv, 1)));
-        }
+        HIP_TRY(ctx, grow(ctx, k.rdev, std::max<uint32_t>(s->n_rdev, 1)));
+        HIP_TRY(ctx, grow(ctx, k.gnodes, std::max<uint32_t>(s->n_gnodes, 1)));
+        HIP_TRY(ctx, grow(ctx, k.grsv, std::max<uint32_t>(s->n_grsv, 1)));
         k.nrd = s->n_rdev, k.ngn = s->n_gnodes, k.ngr = s->n_grsv;
         if (s->n_rdev) HIP_TRY(ctx, hipMemcpyAsync(k.rdev, s->d_rdev, sizeof(DevRec) * s->n_rdev, hipMemcpyDeviceToDevice, ctx->stream));
         if (s->n_gnodes)
@@ -3922,7 +3728,7 @@ kg_status kg_batch_schedule(kg_snap* s, kg_pods* p, const int32_t* plan_node, ui
     // device scratch: [begin G+1][pods n][rec G] + outputs [result n][status n][zone n][minors n]
     const size_t words = (size_t)G + 1 + n + G + 4 * (size_t)n;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!p->d_batch) HIP_TRY(ctx, hipMalloc(&p->d_batch, sizeof(uint32_t) * (7 * (size_t)p->cap + 1)));
+    HIP_TRY(ctx, p->d_batch.reserve(7 * (size_t)p->cap + 1));
     uint32_t* d = p->d_batch;
     if (words > 7 * (size_t)p->cap + 1) return fail(ctx, KG_INVALID_ARG, "batch scratch");
     std::vector<uint32_t> h(G + 1 + n + G);
@@ -4000,12 +3806,8 @@ kg_status kg_snapshot_upload_quotas(kg_snap* s, const kg_quota_columns* c, uint3
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     s->gen++;
-    hipFree(s->d_qlim);
-    hipFree(s->d_qstate);
-    s->d_qlim = nullptr;
-    s->d_qstate = nullptr;
-    HIP_TRY(ctx, hipMalloc(&s->d_qlim, sizeof(QuotaLim) * lim.size()));
-    HIP_TRY(ctx, hipMalloc(&s->d_qstate, sizeof(QuotaState) * qs.size()));
+    HIP_TRY(ctx, renew(s->d_qlim, lim.size()));
+    HIP_TRY(ctx, renew(s->d_qstate, qs.size()));
     HIP_TRY(ctx, hipMemcpyAsync(s->d_qlim, lim.data(), sizeof(QuotaLim) * lim.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(s->d_qstate, qs.data(), sizeof(QuotaState) * qs.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -4182,25 +3984,15 @@ static kg_status upload_views(kg_snap* s, const kg_rsv_view* views, uint32_t nv,
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (void* b : {(void*)s->d_views, (void*)s->d_infos, (void*)s->d_cls_begin, (void*)s->d_rdev, (void*)s->d_rdev_rec,
-                    (void*)s->d_vfirst, (void*)s->d_vmap})
-        hipFree(b);
-    s->d_vfirst = nullptr;
-    s->d_vmap = nullptr;
-    s->d_views = nullptr;
-    s->d_infos = nullptr;
-    s->d_cls_begin = nullptr;
-    s->d_rdev = nullptr;
-    s->d_rdev_rec = nullptr;
     s->n_rdev = nd;
-    HIP_TRY(ctx, hipMalloc(&s->d_rdev_rec, sizeof(uint32_t) * rrec.size()));
+    HIP_TRY(ctx, renew(s->d_rdev_rec, rrec.size()));
     HIP_TRY(ctx, hipMemcpyAsync(s->d_rdev_rec, rrec.data(), sizeof(uint32_t) * rrec.size(), hipMemcpyHostToDevice, ctx->stream));
     static_assert(sizeof(DevRec) == sizeof(kg_rsv_dev), "kg_rsv_dev is a DevRec");
-    HIP_TRY(ctx, hipMalloc(&s->d_rdev, sizeof(DevRec) * std::max<uint32_t>(nd, 1)));
+    HIP_TRY(ctx, renew(s->d_rdev, std::max<uint32_t>(nd, 1)));
     if (nd) HIP_TRY(ctx, hipMemcpyAsync(s->d_rdev, devs, sizeof(DevRec) * nd, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMalloc(&s->d_views, sizeof(RsvView) * dv.size()));
-    HIP_TRY(ctx, hipMalloc(&s->d_infos, sizeof(RsvInfo) * di.size()));
-    HIP_TRY(ctx, hipMalloc(&s->d_cls_begin, sizeof(uint32_t) * cb.size()));
+    HIP_TRY(ctx, renew(s->d_views, dv.size()));
+    HIP_TRY(ctx, renew(s->d_infos, di.size()));
+    HIP_TRY(ctx, renew(s->d_cls_begin, cb.size()));
     HIP_TRY(ctx, hipMemcpyAsync(s->d_views, dv.data(), sizeof(RsvView) * dv.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(s->d_infos, di.data(), sizeof(RsvInfo) * di.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(s->d_cls_begin, cb.data(), sizeof(uint32_t) * cb.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -4219,8 +4011,8 @@ static kg_status upload_views(kg_snap* s, const kg_rsv_view* views, uint32_t nv,
             vmap[vfirst[r] + (uint32_t)__builtin_popcountll(rmask[r] & ((1ull << dv[t].cls) - 1ull))] = t;
         }
     }
-    HIP_TRY(ctx, hipMalloc(&s->d_vfirst, sizeof(uint32_t) * vfirst.size()));
-    HIP_TRY(ctx, hipMalloc(&s->d_vmap, sizeof(uint32_t) * vmap.size()));
+    HIP_TRY(ctx, renew(s->d_vfirst, vfirst.size()));
+    HIP_TRY(ctx, renew(s->d_vmap, vmap.size()));
     HIP_TRY(ctx, hipMemcpyAsync(s->d_vfirst, vfirst.data(), sizeof(uint32_t) * vfirst.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(s->d_vmap, vmap.data(), sizeof(uint32_t) * vmap.size(), hipMemcpyHostToDevice, ctx->stream));
     // class masks into slot N_RSV_CLASSES of every record (a strided 8-byte column copy)
@@ -4330,11 +4122,9 @@ kg_status kg_snapshot_upload_rsv_gpu(kg_snap* s, const kg_rsv_gpu* g, uint32_t n
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (void* b : {(void*)s->d_graw, (void*)s->d_gnodes, (void*)s->d_grsv}) hipFree(b);
-    s->d_graw = nullptr, s->d_gnodes = nullptr, s->d_grsv = nullptr;
-    HIP_TRY(ctx, hipMalloc(&s->d_graw, sizeof(int32_t) * graw.size()));
-    HIP_TRY(ctx, hipMalloc(&s->d_gnodes, sizeof(GpuRawNode) * std::max<size_t>(gn.size(), 1)));
-    HIP_TRY(ctx, hipMalloc(&s->d_grsv, sizeof(GpuRawRsv) * std::max<size_t>(gr.size(), 1)));
+    HIP_TRY(ctx, renew(s->d_graw, graw.size()));
+    HIP_TRY(ctx, renew(s->d_gnodes, std::max<size_t>(gn.size(), 1)));
+    HIP_TRY(ctx, renew(s->d_grsv, std::max<size_t>(gr.size(), 1)));
     HIP_TRY(ctx, hipMemcpy(s->d_graw, graw.data(), sizeof(int32_t) * graw.size(), hipMemcpyHostToDevice));
     if (!gn.empty()) HIP_TRY(ctx, hipMemcpy(s->d_gnodes, gn.data(), sizeof(GpuRawNode) * gn.size(), hipMemcpyHostToDevice));
     if (!gr.empty()) HIP_TRY(ctx, hipMemcpy(s->d_grsv, gr.data(), sizeof(GpuRawRsv) * gr.size(), hipMemcpyHostToDevice));
@@ -4499,15 +4289,7 @@ kg_status kg_shard_select(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* out_keys
     const uint32_t n = p->n;
     const uint32_t kk = k == 1 ? 1 : KG_TOPK_MAX;  // kernels keep 1 or KG_TOPK_MAX keys per pod
     const size_t need = (size_t)n * kk * (ctx->world + 1);
-    if (need > p->gather_cap) {
-        if (p->d_gather) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipFree(p->d_gather));
-            p->d_gather = nullptr;
-        }
-        HIP_TRY(ctx, hipMalloc(&p->d_gather, sizeof(uint64_t) * std::max<size_t>(need, 1)));
-        p->gather_cap = need;
-    }
+    HIP_TRY(ctx, grow(ctx, p->d_gather, need));
     uint64_t* local = p->d_gather + (size_t)n * kk * ctx->world;  // this shard's per-pod top-kk keys
     if (s->ext()) {
         // NormalizeScore maxima and the Reservation preferred node are global over all shards: one
