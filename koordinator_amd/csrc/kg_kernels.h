@@ -68,6 +68,7 @@ struct LaunchSelect {
     uint32_t small_slices;   // waves sets per workgroup, each walking its part of the workgroup's chunk
     uint32_t small_replicas;  // replicas of the accumulators; they and *sticket are zero before and after every launch
     uint32_t* sticket;        // arrival counter of the launch
+    bool small_rows4;         // lane_of, out and pstat are 16-byte aligned: the finisher stores four rows per thread and step
     // optional timing pair of the small select (both set, or neither): the launch binds ev_start to k_select_small's
     // begin and ev_stop to the end of the kernel that finishes the step (hipExtLaunchKernelGGL), instead of the caller
     // recording events around it. Bound only when launch_select returns hipSuccess

@@ -293,6 +293,7 @@ __global__ __launch_bounds__(256) KG_SEL1_ATTR void k_select1(const NodeRec* __r
 // PH (KG_SMALL_PHASES, a measurement aid; off in every instantiation the library launches by default): prof is set and
 // the launch's own scratch pair, followed by four clock readings per workgroup that thread 0 stores: entry, loops done
 // (after the slices met in LDS), ticket drawn and, the finisher only (else zero), rows stored.
+constexpr uint32_t SMALL_ROW_STEPS = 4;  // the finisher's lane words in flight per thread
 template <uint32_t PM, uint32_t WG, bool PH = false>
 __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__ nodes, const ZoneRec* __restrict__ zones,
                                                            PodsDev pods, uint32_t n_lanes, uint32_t lp, uint32_t n0,
@@ -303,7 +304,7 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
                                                            uint32_t* __restrict__ ticket,
                                                            const uint8_t* __restrict__ lane_of, uint32_t n_rows,
                                                            uint64_t* __restrict__ out, uint32_t* __restrict__ pstat,
-                                                           uint64_t* __restrict__ prof) {
+                                                           uint64_t* __restrict__ prof, uint32_t rows4) {
     __shared__ uint64_t lk[WG];
     __shared__ uint2 ls[WG];
     uint64_t ph_entry = 0, ph_loops = 0;
@@ -465,7 +466,34 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
         lk[j] = top;
     }
     __syncthreads();
-    for (uint32_t r = threadIdx.x; r < n_rows; r += blockDim.x) {
+    // Four rows per thread and step: one 32-bit word of lane_of, then 2 x 16 bytes of keys and 16 bytes of status
+    // (rows4, uniform: lane_of, out and pstat are 16-byte aligned, the host checks it; else every row goes through
+    // the loop below). A thread issues the lane words of SMALL_ROW_STEPS steps before its first store, so up to 16
+    // rows x the workgroup's threads cost one load round trip; a one-byte load and two stores per thread and 1,024
+    // rows made ten load-then-store round trips of 10,000 rows (the stores count on the loads' counter). The rows
+    // past the last multiple of four go one by one.
+    const uint32_t n4 = rows4 ? n_rows / 4u : 0u;
+    const uint32_t* const lane4 = reinterpret_cast<const uint32_t*>(lane_of);
+    for (uint32_t q0 = threadIdx.x; q0 < n4; q0 += SMALL_ROW_STEPS * blockDim.x) {
+        uint32_t w[SMALL_ROW_STEPS];
+#pragma unroll
+        for (uint32_t u = 0; u < SMALL_ROW_STEPS; u++) {
+            const uint32_t q = q0 + u * blockDim.x;
+            w[u] = q < n4 ? lane4[q] : 0u;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < SMALL_ROW_STEPS; u++) {
+            const uint32_t q = q0 + u * blockDim.x;
+            if (q < n4) {
+                const uint32_t l0 = w[u] & 255u, l1 = (w[u] >> 8) & 255u, l2 = (w[u] >> 16) & 255u, l3 = w[u] >> 24;
+                ulonglong2* const o = reinterpret_cast<ulonglong2*>(out + 4u * (size_t)q);
+                o[0] = make_ulonglong2(lk[l0], lk[l1]);
+                o[1] = make_ulonglong2(lk[l2], lk[l3]);
+                *reinterpret_cast<uint4*>(pstat + 4u * (size_t)q) = make_uint4(ls[l0].x, ls[l1].x, ls[l2].x, ls[l3].x);
+            }
+        }
+    }
+    for (uint32_t r = 4u * n4 + threadIdx.x; r < n_rows; r += blockDim.x) {
         const uint32_t l = lane_of[r];
         out[r] = lk[l];
         pstat[r] = ls[l].x;
@@ -1366,7 +1394,8 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
     const hipEvent_t sel_stop = a.small_replicas ? a.ev_stop : nullptr;  // two launches: k_small_finish ends the step
 #define KG_SMALL_ARGS                                                                                                 \
     a.nodes, a.zones, a.pods, a.n_fast, lp, r0.end, r1.end, r0.chunk, r1.chunk, r1.n_chunks, a.index_base, a.cfg,      \
-        a.skeys, a.sub, a.sfhi, a.order, a.small_replicas, a.sticket, a.lane_of, a.n_rows, a.out, a.pstat, a.prof
+        a.skeys, a.sub, a.sfhi, a.order, a.small_replicas, a.sticket, a.lane_of, a.n_rows, a.out, a.pstat, a.prof,    \
+        a.small_rows4 ? 1u : 0u
 #define KG_SMALL_WG(PMV, WGV)                                                                                         \
     do {                                                                                                              \
         if (timed)                                                                                                    \

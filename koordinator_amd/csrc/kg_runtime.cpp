@@ -2509,13 +2509,28 @@ static uint32_t device_cus(kg_ctx* ctx) {
 // every lane a fast lane and at most 256 of them, with or without the pod-row reduction. Sets a's geometry for it. A
 // workgroup holds SMALL_COPIES_* copies of the lanes and, with its registers, has a compute unit to itself, so the
 // launch is fastest as one round of workgroups: the chunk lengths are derived from the class lengths so that the
-// chunks number about SMALL_FILL of the device's compute units, a class-1 record counting as 4/3 of a class-0 one
-// (its chunks are 3/4 as long); between SMALL_MIN_CHUNK and SMALL_MAX_CHUNK records, so a large snapshot runs several
-// rounds, and one that needs more than SMALL_MAX_CHUNKS chunks keeps the general path. KG_NO_SMALL_SELECT (read per
+// chunks number about SMALL_FILL of the device's compute units; between SMALL_MIN_CHUNK and SMALL_MAX_CHUNK records,
+// so a large snapshot runs several rounds, and one that needs more than SMALL_MAX_CHUNKS chunks keeps the general
+// path. Above one wave of lanes a class-1 record counts as two class-0 ones (its chunks are half as long) and the
+// fill is 63/64, with the chunks lengthened while their rounded counts exceed the compute units (one workgroup alone
+// in a second round costs a third more: 46 / 24 records, 259 workgroups, 0.0236 ms). Measured on config 2 at 145
+// lanes (tools/small_phases_by_chunk.py, tools/small_select_ab.py --sweep and --phases, profiles/small_warm/): at 3/4
+// and 7/8 (48 / 36 records, 223 workgroups) a class-1 workgroup took 12.3 us for its loops and a class-0 one 10.2, and
+// the launch ends with its slowest workgroup, through after 13.8 to 14.0 us; at 48 / 24 (251 workgroups) 9.8 against
+// 10.3, the slowest through after 12.6 to 12.7 us. In the sweep (no profiling, 4 repeats, spread 0.0001 to 0.0002 ms)
+// 48 / 36 takes 0.0171-0.0174, 48 / 24 0.0169-0.0170, 48 / 32 0.0166-0.0168, 46 / 26 0.0164-0.0165; which class-1
+// length between 24 and 32 is best differs from run to run, each of them beats 36 in all, and longer chunks at the
+// same ratio lose it again (50 / 28, 54 / 27: as 48 / 36). The headline is bench.py's: 0.0205 -> 0.0187 ms.
+// 256 lanes 0.0194 -> 0.0181 ms, config 4's 100,000 nodes (several rounds) 0.130 -> 0.102. At 64 lanes (16 copies,
+// two or three records each) the loops are short and 28 more workgroups cost more at entry and hand-off than the
+// balance gains, 0.0121 -> 0.0127: one wave of lanes keeps 3/4 and 7/8. So does a table with F_BIG records: their
+// inline integer path decides which workgroup is last, by where the chunk borders fall (0.4 % F_BIG records: 0.0447
+// to 0.0489 ms over class-0 lengths 37 to 40 at either ratio, 0.0555 at the new rule's own choice against 0.0463;
+// 0.2 %: 0.0408 either way), and a fuller chip leaves it no idle neighbours. KG_NO_SMALL_SELECT (read per
 // call) keeps the general path too; KG_SMALL_CHUNKS="c0,c1,copies" sets the geometry (measurement aid).
 // threads that the copies of the lanes may fill (512: the launch-bound variant without scratch; 1024: the spilling one)
-constexpr uint32_t SMALL_COPIES_WG = 1024, SMALL_BIG_DEN = 250;
-constexpr uint32_t SMALL_MIN_CHUNK = 8, SMALL_FILL_NUM = 7, SMALL_FILL_DEN = 8;
+constexpr uint32_t SMALL_COPIES_WG = 1024, SMALL_BIG_DEN = 250, SMALL_BIG_EVEN_DEN = 400;
+constexpr uint32_t SMALL_MIN_CHUNK = 8, SMALL_FILL_NUM = 63, SMALL_FILL_DEN = 64;
 // The finish inside the launch: the workgroups fold into SMALL_REPLICAS replicas of the accumulators, whatever the chunk
 // count. Measured (tools/small_select_ab.py --replicas, profiles/small_fused/replicas_*.jsonl, ms per select by replica
 // count 1 / 4 / 8 / 16 / 32 / 64 / one per chunk, then the two launches): config 2 at 145 lanes (223 chunks) 0.0185 /
@@ -2542,11 +2557,19 @@ static bool select_small(const kg_snap* s, LaunchSelect& a) {
     const uint32_t lp = (a.n_fast + 63) / 64 * 64;
     const uint32_t len0 = a.range[0].end - a.range[0].begin, len1 = a.range[1].end - a.range[1].begin;
     const uint32_t cus = std::max<uint32_t>(device_cus(s->ctx), 8u);
-    const uint32_t want = std::max<uint32_t>(1u, cus * SMALL_FILL_NUM / SMALL_FILL_DEN);
-    const uint64_t work = (uint64_t)len0 * 3 + (uint64_t)len1 * 4;  // in thirds of a class-0 record
+    // one wave of lanes, or F_BIG records above 1 in SMALL_BIG_EVEN_DEN: 3/4 and 7/8, see above
+    const bool narrow = lp <= 64 || (uint64_t)s->n_big_est * SMALL_BIG_EVEN_DEN > s->n;
+    const uint32_t want = std::max<uint32_t>(1u, narrow ? cus * 7 / 8 : cus * SMALL_FILL_NUM / SMALL_FILL_DEN);
+    // a class-1 chunk is rn / rd as long as a class-0 one; the work in 1 / rn of a class-0 record
+    const uint32_t rn = narrow ? 3 : 1, rd = narrow ? 4 : 2;
+    const uint64_t work = (uint64_t)len0 * rn + (uint64_t)len1 * rd;
+    const auto chunk1_of = [&](uint32_t c0) { return std::max<uint32_t>(1u, narrow ? c0 * 3 / 4 : (c0 + 1) / 2); };
+    const auto chunks_at = [&](uint32_t c0) { return (len0 + c0 - 1) / c0 + (len1 + chunk1_of(c0) - 1) / chunk1_of(c0); };
     uint32_t chunk[2];
-    chunk[0] = (uint32_t)std::min<uint64_t>(SMALL_MAX_CHUNK, std::max<uint64_t>(SMALL_MIN_CHUNK, (work + 3ull * want - 1) / (3ull * want)));
-    chunk[1] = std::max<uint32_t>(1u, chunk[0] * 3 / 4);
+    chunk[0] = (uint32_t)std::min<uint64_t>(SMALL_MAX_CHUNK, std::max<uint64_t>(SMALL_MIN_CHUNK, (work + (uint64_t)rn * want - 1) / ((uint64_t)rn * want)));
+    // the rounding of the two chunk counts may take them past the compute units: no second round for a few workgroups
+    while (!narrow && chunk[0] < SMALL_MAX_CHUNK && chunks_at(chunk[0]) > cus && chunks_at(chunk[0]) < 2 * cus) chunk[0]++;
+    chunk[1] = chunk1_of(chunk[0]);
     a.small_slices = SMALL_COPIES_WG / lp;
     if (const char* e = std::getenv("KG_SMALL_CHUNKS")) {
         unsigned c0 = 0, c1 = 0, sl = 0;
@@ -2742,6 +2765,12 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
             a.sfhi = a.sub + slots;
         }
         a.lane_of = dd ? p->d_rlane : p->d_lane;
+        // The finisher's 16-byte row stores and 4-byte lane loads need aligned tables. The lane tables are 256-byte
+        // aligned regions of the batch's input buffer (pod_layout), d_pstat and a batch's own d_keys are allocations;
+        // a sharded select's d_out lies n x world keys into the gather buffer, 8-byte aligned only when that is odd:
+        // checked here, and such a launch stores its rows one by one
+        const auto aligned16 = [](const void* q) { return reinterpret_cast<uintptr_t>(q) % 16u == 0; };
+        a.small_rows4 = aligned16(a.lane_of) && aligned16(d_out) && aligned16(p->d_pstat.get());
         // kernel-time bracket (kg_profile_read). One launch: the kernel times itself with the device clock (a.prof; the
         // begin word lies in the batch's accumulator buffer, so sacc_dirty clears it too), the launch is the plain one
         // and the host only counts it, once it succeeded. Two launches, a device without a wall clock
