@@ -596,6 +596,10 @@ kg_status kg_pods_upload(kg_pods* pods, const kg_pod_columns* cols, uint32_t n_p
  * 64-lane waves (the duplicates' keys and status are copied from their representative on the device; results are the
  * same). fast_lanes: the leading lanes on the float64 fast path. Either pointer may be NULL. Diagnostics only. */
 kg_status kg_pods_select_lanes(const kg_pods* pods, uint32_t* lanes, uint32_t* fast_lanes);
+/* The fast lanes among them on this snapshot: kg_pods_select_lanes' count, or 0 when the snapshot's configuration is
+ * outside the fast path's domain (a per-resource weight above 4096, a LoadAware weight sum above 4096, a MostAllocated
+ * strategy, ignored scalars) or KG_SELECT_INT=1 / the exact mode sends every lane to the integer path. Diagnostics only. */
+kg_status kg_select_fast_lanes(const kg_snap* snap, const kg_pods* pods, uint32_t* fast_lanes);
 /* Per-pod candidate node sets: the nodes each pod of the uploaded batch may use, as the scheduler narrowed them before
  * koord's plugins run (nodeSelector and required node affinity, taints and tolerations, spec.nodeName,
  * NodeUnschedulable, PodTopologySpread, a nominated node, a PreFilterResult). A pair (pod j, node i) with i outside j's

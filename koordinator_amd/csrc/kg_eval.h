@@ -1080,6 +1080,9 @@ __device__ __forceinline__ void apply_assume(const KCfg& c, int64_t* n, ZoneRec*
 // Weighted mean Σ s_i w_i / Σ w_i (s_i <= 100, host-checked w_i <= 4096, Σ w_i <= 16384): with
 // doubled weights, trunc((2 Σ s_i w_i + 1) * (0.5 / Σ w_i)) in float32: the exact value sits at least
 // 0.5/Σw (>= 3.05e-5) away from any integer and the float error is <= 101 * 1.5 * 2^-23 (1.8e-5).
+// (tests/test_mean_margin.py walks the whole domain in float32: right for the nearest float to 0.5/Σw and one ulp to
+// either side, wrong from two ulp above. The Newton step after the hardware reciprocal is therefore margin, not
+// needed while that reciprocal keeps its documented 1 ulp; the "+ 1" is needed, e.g. at Σw = 41.)
 
 struct PodF {
     double cpu, mem, eph, sc0, sc1, nzc, nzm, e0, e1;  // x100

@@ -142,7 +142,9 @@ __global__ __launch_bounds__(256) void k_int_seed(const NodeRec* __restrict__ no
     if (unsup) atomicOr(pstat + (pmap ? pmap[row] : row), unsup);
 }
 
-template <int K>
+// PP: the enabled ones of NodeResourcesFit and LoadAware (cfg.plugins & 3): the prune may drop a pair only on a filter
+// that eval_pair applies too, and its bound adds the scores eval_pair adds
+template <int K, uint32_t PP>
 __global__ __launch_bounds__(256) void k_int_filter(const NodeRec* __restrict__ nodes, const ZoneRec* __restrict__ zones,
                                                     PodsDev pods, uint32_t n_lanes, const uint32_t* __restrict__ order,
                                                     uint32_t begin, uint32_t end, uint32_t chunk, uint32_t index_base,
@@ -173,7 +175,7 @@ __global__ __launch_bounds__(256) void k_int_filter(const NodeRec* __restrict__ 
         if (fastv && !((uint32_t)nv[N_FLAGS] & F_VBIG)) {
             const FastRec& fr = *reinterpret_cast<const FastRec*>(&nv[FAST_BEGIN]);
             uint32_t part = 0;
-            const bool ok = fast_eval<KG_PLUGIN_NRF | KG_PLUGIN_LA, 0>(cv, fr, zones + i, pf, part);
+            const bool ok = fast_eval<PP, 0>(cv, fr, zones + i, pf, part);
             keep = ok && ((((uint64_t)(part + bonus)) << 32) | 0xFFFFFFFFull) >= floor_key;
         }
         const uint64_t bk = __ballot(keep);
@@ -364,7 +366,7 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
         if (!((uint32_t)nv[N_FLAGS] & F_VBIG)) {
             const FastRec& fr = *reinterpret_cast<const FastRec*>(&nv[FAST_BEGIN]);
             uint32_t part = 0;
-            const bool ok = fast_eval<KG_PLUGIN_NRF | KG_PLUGIN_LA, 0>(cv, fr, zones + i, pf, part);
+            const bool ok = fast_eval<PM & (KG_PLUGIN_NRF | KG_PLUGIN_LA), 0>(cv, fr, zones + i, pf, part);
             const uint32_t b = part + (uint32_t)cfg.w_numa * 100u;
             const uint64_t bound = ((uint64_t)b << 32) | 0xFFFFFFFFull;
             need = need && ok && bound >= floor_key;
@@ -602,7 +604,7 @@ __global__ __launch_bounds__(SMALL_FIN_WG) void k_small_finish(const uint64_t* _
 // device's F_BIG list (k_big_scan), whose length is only known on the device: gridDim.y chunks of
 // ceil(count / gridDim.y) records each. K == 1 with `out`: atomicMax into out[row]; else the lane's top-K
 // into partial row part0 + blockIdx.y (empty chunks write zeros).
-template <int K>
+template <int K, uint32_t PP>
 __global__ __launch_bounds__(256) void k_big_sel(const NodeRec* __restrict__ nodes, const ZoneRec* __restrict__ zones,
                                                  PodsDev pods, uint32_t n_lanes, uint32_t ld,
                                                  const uint32_t* __restrict__ big_list,
@@ -644,8 +646,8 @@ __global__ __launch_bounds__(256) void k_big_sel(const NodeRec* __restrict__ nod
             if (direct && !(fl & F_VBIG)) {
                 const FastRec& fr = *reinterpret_cast<const FastRec*>(&nv[FAST_BEGIN]);
                 uint32_t part = 0;
-                const bool ok = fast_eval<KG_PLUGIN_NRF | KG_PLUGIN_LA, 0>(cv, fr, zones + i, pf, part);
-                if (!ok) continue;  // the pair fails NodeResourcesFit / LoadAware: key 0
+                const bool ok = fast_eval<PP, 0>(cv, fr, zones + i, pf, part);
+                if (!ok) continue;  // the pair fails an enabled one of NodeResourcesFit / LoadAware: key 0
                 const uint64_t bound = ((uint64_t)(part + (uint32_t)cfg.w_numa * 100u) << 32) | 0xFFFFFFFFull;
                 if (bound < floor_key) continue;
             }
@@ -1441,6 +1443,36 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
     return KG_LAUNCH_CHECK();
 }
 
+// The two pruning kernels, instantiated per enabled subset of NodeResourcesFit / LoadAware (their PP)
+template <int K>
+static void int_filter(const LaunchSelect& a, dim3 grid, uint32_t n_int, const uint32_t* io, uint32_t seed_n, uint32_t chunk,
+                       hipStream_t s) {
+#define KG_INT_FILTER(PPV)                                                                                          \
+    k_int_filter<K, PPV><<<grid, 256, 0, s>>>(a.nodes, a.zones, a.pods, n_int, io, seed_n, a.irange.end, chunk,     \
+                                              a.index_base, a.cfg, a.out, a.ipairs, a.ipair_count)
+    switch (a.cfg.plugins & 3u) {
+        case 0: KG_INT_FILTER(0); break;
+        case 1: KG_INT_FILTER(1); break;
+        case 2: KG_INT_FILTER(2); break;
+        default: KG_INT_FILTER(3); break;
+    }
+#undef KG_INT_FILTER
+}
+
+template <int K>
+static void big_sel(const LaunchSelect& a, dim3 grid, uint32_t n_fast, uint64_t* out, hipStream_t s) {
+#define KG_BIG_SEL(PPV)                                                                                             \
+    k_big_sel<K, PPV><<<grid, 256, 0, s>>>(a.nodes, a.zones, a.pods, n_fast, a.n_rows, a.big_list, a.big_count,     \
+                                           a.index_base, a.cfg, a.partial, a.big_part0, out, a.pmap, a.pstat, a.order)
+    switch (a.cfg.plugins & 3u) {
+        case 0: KG_BIG_SEL(0); break;
+        case 1: KG_BIG_SEL(1); break;
+        case 2: KG_BIG_SEL(2); break;
+        default: KG_BIG_SEL(3); break;
+    }
+#undef KG_BIG_SEL
+}
+
 hipError_t launch_select(const LaunchSelect& a, hipStream_t s) {
     if (a.small) return launch_select_small(a, s);
     const uint32_t K = a.k == 1 ? 1u : (uint32_t)KG_TOPK_MAX;
@@ -1475,9 +1507,7 @@ hipError_t launch_select(const LaunchSelect& a, hipStream_t s) {
         if (K == 1) {
             if (seed_n) k_int_seed<1><<<dim3(i_lb, sy), 256, 0, si>>>(a.nodes, a.zones, a.pods, n_int, io, seed_n, a.index_base,
                                                                      a.cfg, a.out, a.pmap, a.pstat);
-            if (i_fy) k_int_filter<1><<<dim3(i_lb, i_fy), 256, 0, si>>>(a.nodes, a.zones, a.pods, n_int, io, seed_n,
-                                                                       a.irange.end, i_chunk, a.index_base, a.cfg, a.out,
-                                                                       a.ipairs, a.ipair_count);
+            if (i_fy) int_filter<1>(a, dim3(i_lb, i_fy), n_int, io, seed_n, i_chunk, si);
             if (n_segs) k_int_pairs<1><<<min(n_segs, 4096u), 256, 0, si>>>(a.nodes, a.zones, a.pods, io, a.ipairs, a.ipair_count,
                                                                           n_segs, 256u * i_chunk, a.index_base, a.cfg, a.out,
                                                                           a.pmap, a.pstat);
@@ -1485,10 +1515,7 @@ hipError_t launch_select(const LaunchSelect& a, hipStream_t s) {
             if (seed_n)
                 k_int_seed<KG_TOPK_MAX><<<dim3(i_lb, sy), 256, 0, si>>>(a.nodes, a.zones, a.pods, n_int, io, seed_n, a.index_base,
                                                                        a.cfg, a.out, a.pmap, a.pstat);
-            if (i_fy)
-                k_int_filter<KG_TOPK_MAX><<<dim3(i_lb, i_fy), 256, 0, si>>>(a.nodes, a.zones, a.pods, n_int, io, seed_n,
-                                                                           a.irange.end, i_chunk, a.index_base, a.cfg, a.out,
-                                                                           a.ipairs, a.ipair_count);
+            if (i_fy) int_filter<KG_TOPK_MAX>(a, dim3(i_lb, i_fy), n_int, io, seed_n, i_chunk, si);
             if (n_segs)
                 k_int_pairs<KG_TOPK_MAX><<<min(n_segs, 4096u), 256, 0, si>>>(a.nodes, a.zones, a.pods, io, a.ipairs,
                                                                             a.ipair_count, n_segs, 256u * i_chunk,
@@ -1542,15 +1569,9 @@ hipError_t launch_select(const LaunchSelect& a, hipStream_t s) {
         // F_BIG records of the fast lanes: integer path, chunked over the device's list; after the fast records'
         // kernels, whose keys in out let a direct launch skip records that cannot enter the pod's top-K
         {
-            dim3 grid(pod_blocks, a.big_y), block(256);
-            if (K == 1)
-                k_big_sel<1><<<grid, block, 0, s>>>(a.nodes, a.zones, a.pods, n_fast, a.n_rows, a.big_list, a.big_count,
-                                                    a.index_base, a.cfg, a.partial, a.big_part0, a.fused ? a.out : nullptr,
-                                                    a.pmap, a.pstat, a.order);
-            else
-                k_big_sel<KG_TOPK_MAX><<<grid, block, 0, s>>>(a.nodes, a.zones, a.pods, n_fast, a.n_rows, a.big_list,
-                                                              a.big_count, a.index_base, a.cfg, a.partial, a.big_part0,
-                                                              a.fused_k ? a.out : nullptr, a.pmap, a.pstat, a.order);
+            const dim3 grid(pod_blocks, a.big_y);
+            if (K == 1) big_sel<1>(a, grid, n_fast, a.fused ? a.out : nullptr, s);
+            else big_sel<KG_TOPK_MAX>(a, grid, n_fast, a.fused_k ? a.out : nullptr, s);
         }
         if (!a.fused && !a.fused_k) {
             hipError_t e = launch_merge_list(a.partial, 0, select_fparts(a), a.n_rows, a.order, n_fast, K, a.out, s);

@@ -726,13 +726,10 @@ bool unfused() {
     return v == 1;
 }
 
+// KG_SELECT_INT=1: every lane on the integer path (read per call, like KG_NO_IPRUNE: the tests switch it)
 bool force_int() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = std::getenv("KG_SELECT_INT");
-        v = (e && e[0] == '1') ? 1 : 0;
-    }
-    return v == 1;
+    const char* e = std::getenv("KG_SELECT_INT");
+    return e && e[0] == '1';
 }
 
 // Node chunk of the select kernel: enough (pod-block, chunk) workgroups to fill 256 CUs several
@@ -2255,6 +2252,10 @@ static kg_status ext_stats_local(kg_snap* s, kg_pods* p, bool gated = false) {
 // partial rows it needs (row stride n_rows). F_BIG records are spread over big_y chunks sized for ~2048
 // workgroups from the snapshot's F_BIG count at its last upload (the device list may have grown since:
 // the chunks then just get longer).
+// whether a plain select on this snapshot has fast lanes at all: not in the exact / integer modes, and only with
+// weights and strategies inside the fast path's domain (weights_small, kg_snapshot_create)
+static bool plain_fast(const kg_snap* s) { return !force_exact() && !force_int() && s->weights_small; }
+
 static LaunchSelect make_select(const kg_snap* s, const PodsDev& pods, const uint32_t* order, uint32_t n_lanes,
                                 uint32_t n_fast, uint32_t n_rows, uint32_t kk, bool fast, uint64_t* out,
                                 const uint32_t* pmap, uint32_t* pstat, uint32_t* parts) {
@@ -2267,7 +2268,7 @@ static LaunchSelect make_select(const kg_snap* s, const PodsDev& pods, const uin
     a.index_base = s->base;
     a.k = kk;
     a.exact = force_exact();
-    a.fast = fast && !a.exact && !force_int() && s->weights_small;
+    a.fast = fast && plain_fast(s);
     a.n_fast = a.fast ? n_fast : 0;
     a.cfg = s->kcfg;
     a.pmap = pmap;
@@ -2894,6 +2895,13 @@ kg_status kg_pods_select_lanes(const kg_pods* p, uint32_t* lanes, uint32_t* fast
     const bool dd = dedup_on(p);
     if (lanes) *lanes = dd ? p->n_rep : p->n;
     if (fast_lanes) *fast_lanes = dd ? p->n_rep_fast : p->n_fast;
+    return KG_OK;
+}
+
+kg_status kg_select_fast_lanes(const kg_snap* s, const kg_pods* p, uint32_t* fast_lanes) {
+    if (!s || !p || !fast_lanes || s->ctx != p->ctx) return KG_INVALID_ARG;
+    std::lock_guard<std::mutex> g(p->ctx->mu);
+    *fast_lanes = plain_fast(s) ? (dedup_on(p) ? p->n_rep_fast : p->n_fast) : 0u;
     return KG_OK;
 }
 

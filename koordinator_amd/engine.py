@@ -384,6 +384,15 @@ class PodBatch:
         self.ctx.check(self.ctx.L.kg_pods_select_lanes(self.h, C.byref(lanes), C.byref(fast)), "kg_pods_select_lanes")
         return lanes.value, fast.value
 
+    def fast_lanes(self, snap) -> int:
+        """kg_select_fast_lanes: the fast lanes the next plain select of this batch launches on `snap` (0: every lane
+        on the integer path)."""
+        fast = C.c_uint32()
+        fn = self.ctx.L.kg_select_fast_lanes  # bound here: a diagnostic, so A/B runs can still load an older library
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)], C.c_int
+        self.ctx.check(fn(snap.h, self.h, C.byref(fast)), "kg_select_fast_lanes")
+        return fast.value
+
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
             self.ctx.L.kg_pods_destroy(self.h)
