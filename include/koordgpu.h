@@ -191,6 +191,16 @@ typedef enum kg_status {
 #define KG_ST_DEV_RSV 0x40000000u          /* "Reservation(s) Insufficient gpu devices": the pod must allocate from a
                                             * matched reservation and none fits (deviceshare/reservation.go:404-406) */
 #define KG_ST_UNSUPPORTED 0x80000000u /* pair needs the host path (e.g. cpuset binding)        */
+/* The bits above whose status is UnschedulableAndUnresolvable in the reference (preemption cannot help on that node):
+ * KG_ST_NUMA_CONFLICT (nodenumaresource/plugin.go:380), KG_ST_NUMA_CPU_TOPO (:403), KG_ST_NUMA_CPU_BIND (:342, :413,
+ * :418) and KG_ST_DEV_NO_DEVICE (deviceshare/devicehandler_gpu.go:43). kg_eval_feasible with this fail_mask gives the
+ * nodes where preemption might help. KG_ST_NODE_EXCLUDED is left out: the host knows which of its own Filters was
+ * unresolvable. The DeviceShare reason is a 4-bit code, not a bit per reason: KG_ST_DEV_NO_DEVICE is also the low half's
+ * bit 1 of the allocator codes 3, 6, 7, 10 and 11, of which KG_DEV_CODE_GPU_DEVICES (3) is plain Unschedulable in the
+ * reference (allocator_gpu.go:334), and the unresolvable codes 8 and 9 carry no bit of the mask. On pairs with a GPU
+ * allocator code the mask is therefore approximate; a caller that needs them exact reads KG_ST_DEV_CODE of
+ * kg_eval_verify's word. */
+#define KG_ST_UNRESOLVABLE_MASK 0x02620000u
 
 typedef struct kg_ctx kg_ctx;   /* one per device per scheduler profile */
 typedef struct kg_snap kg_snap; /* device-resident node snapshot (one shard) */
@@ -676,6 +686,30 @@ kg_status kg_result_status(kg_pods* pods, uint32_t* out_status);
 #define KG_DIAG_FIRST_PLUGIN 0x1u
 kg_status kg_eval_diagnose(kg_snap* snap, kg_pods* pods, const uint32_t* rows, uint32_t n_rows, uint32_t flags,
                            uint32_t* out_counts /* n_rows * KG_DIAG_SLOTS */);
+/* Feasible-node bitmaps: per requested pod, which nodes of this snapshot pass Filter (one bit per pair instead of
+ * kg_eval_verify's matrix). A framework-mode plugin returns row 0 as PreFilterResult{NodeNames}, serves Filter from
+ * it and hands the feasible nodes to the Score plugins that stay on the host.
+ *   out_bits[t * W + w], W = (n_nodes + 31) / 32, w < W: bit (i & 31) of word (i >> 5) is set iff
+ *            (status word of pair (rows[t], node at snapshot position i) & fail_mask) == 0. The status word is the
+ *            one kg_eval_verify reports for the pair: a batch with candidate node sets includes KG_ST_NODE_EXCLUDED,
+ *            a config-5 snapshot includes the ElasticQuota gate's KG_ST_QUOTA on every node of a rejected pod. Bits
+ *            at or above n_nodes in the last word are 0.
+ *   fail_mask  0xFFFFFFFF: the feasible set. KG_ST_UNRESOLVABLE_MASK: the nodes where preemption might help (upstream's
+ *            nodesWherePreemptionMightHelp drops the UnschedulableAndUnresolvable ones). KG_ST_UNSUPPORTED: the
+ *            complement of the pairs that need the host path. 0: every node bit set.
+ *   rows     as kg_eval_diagnose: batch indices, repeats and any order allowed; NULL: every pod (n_rows must equal the
+ *            batch size).
+ *   out_count (may be NULL): [n_rows] population count of each row.
+ * The format is kg_node_sets.bits': a row can be handed back to kg_pods_set_node_sets, and the rows of node shards
+ * concatenate by words when the shard sizes are multiples of 32 (else the caller shifts); each shard's call returns
+ * its own nodes. index_base is not added.
+ * Synchronous like kg_eval_diagnose, with its precondition checks in its order (KG_UNSUPPORTED for a batch with
+ * candidate node sets on a snapshot with config-5 tables). It changes no state of the snapshot, the batch's keys or
+ * kg_result_status. KG_INVALID_ARG: out_bits == NULL with n_rows > 0, a row >= the batch size, rows == NULL with
+ * another n_rows. n_rows == 0 writes nothing; a snapshot of 0 nodes writes nothing to out_bits (0 words per row) and
+ * zeros to out_count. The symbol is new within ABI 14: a binding resolves it at load time. */
+kg_status kg_eval_feasible(kg_snap* snap, kg_pods* pods, const uint32_t* rows, uint32_t n_rows, uint32_t fail_mask,
+                           uint32_t* out_bits /* n_rows * ((n_nodes + 31) / 32) */, uint32_t* out_count /* n_rows */);
 /* Sequential scheduling of pods[0..n) one at a time with Assume applied on the device between pods
  * (the reference's one-pod-per-cycle semantics). out_node[i] = global node index or -1 (no feasible node,
  * or the selected node's Reserve failed: KG_ST_NUMA_INSUF_* in out_reason).

@@ -132,6 +132,8 @@ KG_ST_RSV_MASK = 0x1C000000
 KG_ST_QUOTA = 0x20000000
 KG_ST_DEV_RSV = 0x40000000  # "Reservation(s) Insufficient gpu devices"
 KG_ST_UNSUPPORTED = 0x80000000
+# the UnschedulableAndUnresolvable bits (include/koordgpu.h): kg_eval_feasible's fail_mask of the preemption candidates
+KG_ST_UNRESOLVABLE_MASK = KG_ST_NUMA_CONFLICT | KG_ST_NUMA_CPU_TOPO | KG_ST_NUMA_CPU_BIND | KG_ST_DEV_NO_DEVICE
 # kg_eval_diagnose: counters per requested pod (slot b < 32: nodes with status bit b; KG_DIAG_DEV_CODE0 + c: nodes whose
 # DeviceShare code is c; KG_DIAG_FEASIBLE: nodes with a zero counted word) and its flag
 KG_DIAG_SLOTS = 64

@@ -31,6 +31,7 @@
 #include "kg_dedup.h"
 #include "kg_devmem.h"
 #include "kg_diag.h"
+#include "kg_feasible.h"
 #include "kg_kernels.h"
 #include "kg_layout.h"
 #include "kg_sets.h"
@@ -258,6 +259,12 @@ struct kg_pods {
     DevBuf<uint32_t> d_diag_rows;
     DevBuf<uint32_t> d_diag;
     size_t diag_cap = 0;  // rows
+    // kg_eval_feasible: the requested rows, their record-order bitmap (step 1), the snapshot-order output (step 2) and
+    // the per-row population counts, grown on demand (ensure_feasible)
+    DevBuf<uint32_t> d_feas_rows;
+    DevBuf<uint64_t> d_feas_rtab;
+    DevBuf<uint32_t> d_feas_out;
+    DevBuf<uint32_t> d_feas_count;
     DevBuf<DevSum> d_devsum;    // per record DevSum of the last config-5 select
     DevBuf<uint64_t> d_gz;      // gpu_zone_sum per (class-1 record, GPU request class) of the last config-5 select
     DevBuf<uint8_t> d_rcode;    // [kg_rsv_dev table][DEV_CLASSES]: GPU allocator outcome on the restore tables
@@ -1995,6 +2002,79 @@ kg_status kg_eval_diagnose(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_
                                  s->kcfg, force_exact(), p->d_qst, (flags & KG_DIAG_FIRST_PLUGIN) != 0, p->d_diag,
                                  ctx->stream, p->any_set ? p->d_pod_set : nullptr, p->d_set_tab, sets_words(s->n)));
     HIP_TRY(ctx, hipMemcpyAsync(out_counts, p->d_diag, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KG_OK;
+}
+
+// Scratch of kg_eval_feasible for n_rows requested rows over n_nodes nodes: no allocation on the steady path. Each
+// buffer keeps its own capacity (DevBuf::cap), so a failed grow leaves nothing to reset.
+static kg_status ensure_feasible(kg_pods* p, size_t n_rows, uint32_t n_nodes) {
+    kg_ctx* ctx = p->ctx;
+    const size_t rows = std::max<size_t>(n_rows, 64);
+    HIP_TRY(ctx, grow(ctx, p->d_feas_rows, rows));
+    HIP_TRY(ctx, grow(ctx, p->d_feas_count, rows));
+    HIP_TRY(ctx, grow(ctx, p->d_feas_rtab, rows * feasible_words(n_nodes)));
+    HIP_TRY(ctx, grow(ctx, p->d_feas_out, rows * feasible_words32(n_nodes)));
+    return KG_OK;
+}
+
+kg_status kg_eval_feasible(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_t n_rows, uint32_t fail_mask,
+                           uint32_t* out_bits, uint32_t* out_count) {
+    kg_status st = check_pair(s, p);
+    if (st != KG_OK) return st;
+    kg_ctx* ctx = s->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!rows && n_rows != p->n)
+        return fail(ctx, KG_INVALID_ARG, "rows == NULL with n_rows %u != batch size %u", n_rows, p->n);
+    if (rows)
+        for (uint32_t t = 0; t < n_rows; t++)
+            if (rows[t] >= p->n) return fail(ctx, KG_INVALID_ARG, "rows[%u] = %u >= batch size %u", t, rows[t], p->n);
+    if (!out_bits && n_rows) return fail(ctx, KG_INVALID_ARG, "null bitmap output");
+    st = check_views(s);
+    if (st != KG_OK) return st;
+    if (s->ext()) {
+        st = refuse_sets(s, p, "feasible bitmaps on a snapshot with config-5 tables");
+        if (st != KG_OK) return st;
+        st = check_ext(s);
+        if (st != KG_OK) return st;
+    }
+    st = ensure_sets(s, p);
+    if (st != KG_OK) return st;
+    if (n_rows == 0) return KG_OK;
+    if (s->n == 0) {  // 0 words per row
+        if (out_count) std::memset(out_count, 0, sizeof(uint32_t) * n_rows);
+        return KG_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = ensure_feasible(p, n_rows, s->n);
+    if (st != KG_OK) return st;
+    if (rows)
+        HIP_TRY(ctx, hipMemcpyAsync(p->d_feas_rows, rows, sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice, ctx->stream));
+    if (out_count) HIP_TRY(ctx, hipMemsetAsync(p->d_feas_count, 0, sizeof(uint32_t) * n_rows, ctx->stream));
+    const ExtDev e = s->ext_dev();
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    st = record_begin(ctx, &e0, &e1);
+    if (st != KG_OK) return st;
+    hipError_t le = hipSuccess;
+    if (s->ext())  // the ElasticQuota PreFilter of every pod of the batch, as kg_eval_verify runs it
+        le = launch_ext_gate(p->dev, p->n, e, s->cfg.plugins, p->d_qst, nullptr, ctx->stream);
+    if (le == hipSuccess)
+        le = launch_feasible_records(s->d_nodes, s->d_zones, e, s->ext(), p->dev, rows ? p->d_feas_rows : nullptr, n_rows,
+                                     s->n, s->kcfg, force_exact(), p->d_qst, fail_mask, p->d_feas_rtab, ctx->stream,
+                                     p->any_set ? p->d_pod_set : nullptr, p->d_set_tab);
+    if (le == hipSuccess)
+        le = launch_feasible_rows(p->d_feas_rtab, s->d_pos, n_rows, s->n, p->d_feas_out,
+                                  out_count ? p->d_feas_count : nullptr, ctx->stream);
+    if (le != hipSuccess) {
+        bracket_drop(ctx, e0, e1);
+        return fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR, "kg_eval_feasible: %s", hipGetErrorString(le));
+    }
+    st = record_end(ctx, e0, e1);
+    if (st != KG_OK) return st;
+    HIP_TRY(ctx, hipMemcpyAsync(out_bits, p->d_feas_out, sizeof(uint32_t) * (size_t)n_rows * feasible_words32(s->n),
+                                hipMemcpyDeviceToHost, ctx->stream));
+    if (out_count)
+        HIP_TRY(ctx, hipMemcpyAsync(out_count, p->d_feas_count, sizeof(uint32_t) * n_rows, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return KG_OK;
 }

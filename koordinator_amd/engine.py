@@ -83,6 +83,8 @@ def lib():
     L.kg_eval_verify.restype = st
     L.kg_eval_diagnose.argtypes = [vp, vp, P(u32), u32, u32, P(u32)]
     L.kg_eval_diagnose.restype = st
+    L.kg_eval_feasible.argtypes = [vp, vp, P(u32), u32, u32, P(u32), P(u32)]  # new within ABI 14: resolved at load time
+    L.kg_eval_feasible.restype = st
     L.kg_eval_select.argtypes = [vp, vp, u32]
     L.kg_eval_select.restype = st
     L.kg_result_keys.argtypes = [vp, P(u64)]
@@ -428,6 +430,27 @@ def eval_diagnose(snap: Snapshot, pods: PodBatch, rows=None, first_plugin: bool 
     snap.ctx.check(snap.ctx.L.kg_eval_diagnose(snap.h, pods.h, rp, n_rows, flags, out.ctypes.data_as(P)),
                    "kg_eval_diagnose")
     return out[:n_rows]
+
+
+def eval_feasible(snap: Snapshot, pods: PodBatch, rows=None, fail_mask: int = 0xFFFFFFFF, counts: bool = False):
+    """kg_eval_feasible: uint32[n_rows, (n_nodes + 31) // 32], bit (i & 31) of word (i >> 5) of row t set = the status
+    word of (pod rows[t], the node at snapshot position i) has no bit of fail_mask (batch indices in any order, repeats
+    allowed; None = every pod). The format is set_node_sets' bitmap; nodesets.to_mask turns it into bool[n_rows,
+    n_nodes]. counts: also return uint32[n_rows], the rows' population counts."""
+    P = C.POINTER(C.c_uint32)
+    if rows is None:
+        n_rows, rp = pods.n, None
+    else:
+        rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        n_rows = len(rows)
+        rp = (rows if n_rows else np.zeros(1, np.uint32)).ctypes.data_as(P)  # an empty list is not "every pod"
+    words = (snap.n + 31) // 32
+    out = np.zeros((n_rows, words), np.uint32)
+    cnt = np.zeros(max(n_rows, 1), np.uint32)
+    op = (out if out.size else np.zeros(1, np.uint32)).ctypes.data_as(P)
+    snap.ctx.check(snap.ctx.L.kg_eval_feasible(snap.h, pods.h, rp, n_rows, int(fail_mask) & 0xFFFFFFFF, op,
+                                               cnt.ctypes.data_as(P) if counts else None), "kg_eval_feasible")
+    return (out, cnt[:n_rows]) if counts else out
 
 
 def eval_select_async(snap: Snapshot, pods: PodBatch, k: int = 1):

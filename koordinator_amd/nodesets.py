@@ -36,6 +36,15 @@ def unpack(bits, n_nodes: int) -> np.ndarray:
     return np.unpackbits(by, axis=1, bitorder="little")[:, :n_nodes].astype(bool)
 
 
+def to_mask(bits, n_nodes: int) -> np.ndarray:
+    """The inverse of pack for the bitmaps that come back from the device (engine.eval_feasible): uint32[R,
+    words(N)] -> bool[R, N], [R, 0] for 0 nodes. unpack under the name of the direction it is used in there."""
+    n_nodes = int(n_nodes)
+    if n_nodes == 0:
+        return np.zeros((len(np.asarray(bits)), 0), bool)
+    return unpack(bits, n_nodes)
+
+
 def from_mask(mask):
     """bool[P, N] (mask[j, i]: pod j may use the node at snapshot position i) -> (pod_set int32[P], bits uint32[S,
     words(N)]). Equal rows share one set, numbered in order of first appearance; an all-true row becomes -1."""
