@@ -640,6 +640,47 @@ typedef struct kg_node_sets {
     uint32_t n_sets, n_nodes;
 } kg_node_sets;
 kg_status kg_pods_set_node_sets(kg_pods* pods, const kg_node_sets* sets /* NULL clears */);
+/* Per-pod host score terms: the Score plugins that stay on the host (NodeAffinity preferred terms, TaintToleration
+ * PreferNoSchedule, ImageLocality, PodTopologySpread, InterPodAffinity) hand their score lists in, and selectHost runs
+ * over koord's total plus theirs. A row is one plugin's score list for one kind of pod (the preferred weights of one
+ * pod template): pods the plugin scores alike share it, and a pod names up to KG_SCORE_TERMS rows.
+ *   Pod j's feasible candidates are the nodes whose kg_eval_verify status word is 0 (KG_ST_NODE_EXCLUDED of a
+ *   candidate node set included). For term t with row r, m = max raw[r][i] over them; the term's value on a feasible
+ *   candidate i is
+ *     KG_SCORE_RAW                raw[r][i]
+ *     KG_SCORE_NORMALIZE          m == 0 ? 0 : 100 * raw[r][i] / m
+ *     KG_SCORE_NORMALIZE_REVERSE  m == 0 ? 100 : 100 - 100 * raw[r][i] / m
+ *   in integer division (DefaultNormalizeScore(100, reverse), pkg/scheduler/frameworkext/normalize_score.go:24-52 and
+ *   upstream's helper of the same shape). The pair's total is koord's total + the sum over t of weight[r] x value.
+ *   kg_eval_select    (plain snapshots, k = 1..4) keys are the top-k of that total over the feasible candidates; ties
+ *                     go to the lowest snapshot index as before; kg_result_status flags a pod with terms as it flags a
+ *                     set lane (when any candidate pair needs the host path);
+ *   kg_eval_verify    total of a feasible candidate pair is that total; every other column and every infeasible pair
+ *                     are as without terms;
+ *   kg_eval_diagnose, kg_eval_feasible  Filter only: they accept the batch and return what they return without terms.
+ * Called after kg_pods_upload; everything is copied. A later kg_pods_upload clears the terms, scores == NULL clears
+ * them too. Sets and terms are independent: clearing one keeps the other. KG_INVALID_ARG: no batch uploaded, a row id
+ * outside [-1, n_rows), a raw value outside [0, KG_SCORE_RAW_MAX], an unknown mode, a weight above 2^20. An evaluating
+ * call (select, verify) returns KG_INVALID_ARG when its snapshot's node count differs from n_nodes, or when the
+ * snapshot's sum of plugin weights x 100 plus the largest per-pod bound of the terms (sum over t of weight x (100, or
+ * the row's largest raw for KG_SCORE_RAW)) could reach 2^31, the total field of the packed key.
+ * KG_UNSUPPORTED while the batch carries terms: kg_eval_select / kg_eval_verify on a snapshot with config-5 tables
+ * (KG_PLUGIN_EXT), kg_shard_select (the maximum is global over the shards) and kg_replay. kg_batch_schedule,
+ * kg_reserve, kg_assume*, kg_forget* and kg_unreserve name their node themselves and do not read the terms. The symbol
+ * is new within ABI 14: a binding resolves it at load time. */
+#define KG_SCORE_TERMS 4                 /* host score terms per pod */
+#define KG_SCORE_RAW 0u                  /* value = raw */
+#define KG_SCORE_NORMALIZE 1u            /* DefaultNormalizeScore(100, reverse=false) over the pod's feasible candidates */
+#define KG_SCORE_NORMALIZE_REVERSE 2u    /* ... reverse=true */
+#define KG_SCORE_RAW_MAX (1 << 20)
+typedef struct kg_node_scores {
+    const int32_t* pod_terms;  /* [n_pods][KG_SCORE_TERMS]: row id, -1 = unused slot */
+    const int32_t* raw;        /* [n_rows][n_nodes], snapshot positions (index_base not added), 0..KG_SCORE_RAW_MAX */
+    const uint32_t* mode;      /* [n_rows] KG_SCORE_* */
+    const uint32_t* weight;    /* [n_rows] the plugin's weight, 0..2^20 */
+    uint32_t n_rows, n_nodes;
+} kg_node_scores;
+kg_status kg_pods_set_node_scores(kg_pods* pods, const kg_node_scores* scores /* NULL clears */);
 kg_status kg_pods_destroy(kg_pods* pods);
 
 /* Full per-plugin Filter/Score matrix for every (pod, node) pair (the FilterPlugin/ScorePlugin

@@ -153,6 +153,20 @@ class KgNodeSets(C.Structure):
                 ("n_nodes", C.c_uint32)]
 
 
+# kg_pods_set_node_scores: host score terms per pod, the modes of a row and the bound of its raw values
+KG_SCORE_TERMS = 4
+KG_SCORE_RAW = 0
+KG_SCORE_NORMALIZE = 1
+KG_SCORE_NORMALIZE_REVERSE = 2
+KG_SCORE_RAW_MAX = 1 << 20
+
+
+class KgNodeScores(C.Structure):
+    """kg_node_scores: per-pod host score terms (koordinator_amd.nodescores builds the arrays)."""
+    _fields_ = [("pod_terms", C.POINTER(C.c_int32)), ("raw", C.POINTER(C.c_int32)), ("mode", C.POINTER(C.c_uint32)),
+                ("weight", C.POINTER(C.c_uint32)), ("n_rows", C.c_uint32), ("n_nodes", C.c_uint32)]
+
+
 _pf64 = C.POINTER(C.c_double)
 _pi32 = C.POINTER(C.c_int32)
 

@@ -15,6 +15,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -22,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <map>
 #include <mutex>
 #include <tuple>
 #include <string>
@@ -34,6 +36,7 @@
 #include "kg_feasible.h"
 #include "kg_kernels.h"
 #include "kg_layout.h"
+#include "kg_scores.h"
 #include "kg_sets.h"
 
 using namespace kg;
@@ -311,7 +314,8 @@ struct kg_pods {
     // (n_nodes is checked by every evaluating call); any_set: some pod names a set, the lane lists are split: d_order /
     // d_rorder hold the lanes without a set (n_plain_lanes / n_plain_fast of d_order, n_rep_plain / n_rep_plain_fast of
     // d_rorder), d_sorder / d_srorder the pods / representatives with one, sorted by set (kg_dedup.h dedup_split_sets).
-    // n_rep / n_rep_fast count both kinds (the dedup gate and kg_pods_select_lanes).
+    // n_rep / n_rep_fast count both kinds (the dedup gate and kg_pods_select_lanes). The lists are split in the same way
+    // when some pod carries a host score term (lanes_split(), below).
     bool batch_uploaded = false, sets_given = false, any_set = false;
     std::vector<uint8_t> h_wk;        // per pod wave kind (0..2 fast kinds, 3 integer lane), kept by the upload
     std::vector<int32_t> h_pod_set;   // [n]
@@ -333,6 +337,36 @@ struct kg_pods {
         d.words32 = sets_words32(set_n_nodes);
         d.words = sets_words(set_n_nodes);
         d.n_sets = set_n_sets;
+        return d;
+    }
+    // Host score terms (kg_pods_set_node_scores), cleared by every upload, independent of the sets. scores_given: a
+    // descriptor is in force; any_term: some pod names a row: its lane leaves the plain lists as a set lane does, and the
+    // term lanes are the tail of d_sorder / d_srorder (after n_set_lanes / n_rep_set set-only lanes), sorted by (set,
+    // term tuple). any_norm: some pod's term is normalised (pass 1 runs). term_bound: the largest per-pod sum of
+    // weight x (100, or the row's largest raw for KG_SCORE_RAW).
+    bool scores_given = false, any_term = false, any_norm = false;
+    std::vector<int32_t> h_pod_terms;  // [n][KG_SCORE_TERMS]
+    uint32_t score_n_rows = 0, score_n_nodes = 0;
+    uint64_t term_bound = 0;
+    uint32_t n_term_lanes = 0, n_rep_term = 0;
+    DevBuf<int32_t> d_pod_terms;    // [cap][KG_SCORE_TERMS]
+    DevBuf<int32_t> d_score_raw;    // [n_rows][n_nodes] snapshot order
+    DevBuf<int32_t> d_score_rtab;   // [n_rows][n_nodes] record order, for (rtab_uid, rtab_layout)
+    DevBuf<uint32_t> d_score_mode;  // [n_rows]
+    DevBuf<uint32_t> d_score_weight;
+    DevBuf<uint32_t> d_term_max;    // [cap][KG_SCORE_TERMS] pass-1 maxima of the last select
+    bool rtab_valid = false;
+    uint64_t rtab_uid = 0, rtab_layout = 0;
+    bool lanes_split() const { return any_set || any_term; }
+    ScoresDev scores_dev() const {
+        ScoresDev d{};
+        d.pod_terms = d_pod_terms;
+        d.raw = d_score_raw;
+        d.rtab = d_score_rtab;
+        d.mode = d_score_mode;
+        d.weight = d_score_weight;
+        d.n_rows = score_n_rows;
+        d.n_nodes = score_n_nodes;
         return d;
     }
 };
@@ -1684,6 +1718,8 @@ kg_status kg_pods_upload(kg_pods* p, const kg_pod_columns* cols, uint32_t n) {
     // a new batch carries no candidate node sets; the wave kinds stay for kg_pods_set_node_sets' lane lists
     p->batch_uploaded = true;
     p->sets_given = p->any_set = p->tab_valid = false;
+    p->scores_given = p->any_term = p->any_norm = p->rtab_valid = false;  // nor host score terms
+    p->n_term_lanes = p->n_rep_term = 0;
     p->h_wk.assign(wk.begin(), wk.begin() + n);
     p->n_plain_lanes = n;
     p->n_plain_fast = n_fast;
@@ -1694,8 +1730,12 @@ kg_status kg_pods_upload(kg_pods* p, const kg_pod_columns* cols, uint32_t n) {
 }
 
 // Lane lists, rep and the row-to-lane tables of the uploaded batch from its staged rows (still in p->h_in), with the
-// pods' set ids counted as part of the row; set == nullptr: no sets, exactly the lists kg_pods_upload built.
-static kg_status derive_lanes(kg_pods* p, const int32_t* set) {
+// pods' set ids and term tuples (the descriptors in force: p->sets_given / p->scores_given) counted as part of the row.
+// Neither in force: exactly the lists kg_pods_upload built. A pod's set and tuple are folded into one group id for
+// kg_dedup.h (which knows one id per row): -1 for a pod with neither, else the rank of (has a term, set, tuple), so
+// that dedup_split_sets' order by id puts the set-only lanes first, sorted by set, and then the term lanes, sorted by
+// (set, term tuple).
+static kg_status derive_lanes(kg_pods* p) {
     kg_ctx* ctx = p->ctx;
     const uint32_t n = p->n, n_fast = p->n_fast;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1706,8 +1746,40 @@ static kg_status derive_lanes(kg_pods* p, const int32_t* set) {
         HIP_TRY(ctx, hipEventSynchronize(p->in_copied));
         p->in_pending = false;
     }
-    bool any = false;
-    for (uint32_t j = 0; set && j < n; j++) any |= set[j] >= 0;
+    const int32_t* set = p->sets_given ? p->h_pod_set.data() : nullptr;
+    const int32_t* terms = p->scores_given ? p->h_pod_terms.data() : nullptr;
+    const auto has_term = [&](uint32_t j) {
+        bool t = false;
+        for (int u = 0; terms && u < KG_SCORE_TERMS; u++) t |= terms[(size_t)j * KG_SCORE_TERMS + u] >= 0;
+        return t;
+    };
+    bool any_s = false, any_t = false;
+    for (uint32_t j = 0; j < n; j++) {
+        any_s |= set && set[j] >= 0;
+        any_t |= has_term(j);
+    }
+    const bool any = any_s || any_t;
+    std::vector<int32_t> grp;
+    const int32_t* gid = set;  // without terms the set id is the group id
+    if (any_t) {
+        using Key = std::array<int32_t, 2 + KG_SCORE_TERMS>;
+        const auto key = [&](uint32_t j) {
+            Key k{};
+            k[0] = has_term(j);
+            k[1] = set ? set[j] : -1;
+            for (int u = 0; u < KG_SCORE_TERMS; u++) k[2 + u] = terms[(size_t)j * KG_SCORE_TERMS + u];
+            return k;
+        };
+        std::map<Key, int32_t> ids;
+        for (uint32_t j = 0; j < n; j++)
+            if (has_term(j) || (set && set[j] >= 0)) ids.emplace(key(j), 0);
+        int32_t next = 0;
+        for (auto& kv : ids) kv.second = next++;
+        grp.assign(n, -1);
+        for (uint32_t j = 0; j < n; j++)
+            if (has_term(j) || (set && set[j] >= 0)) grp[j] = ids[key(j)];
+        gid = grp.data();
+    }
     if (any) {
         HIP_TRY(ctx, p->d_sorder.reserve(p->cap));
         HIP_TRY(ctx, p->d_srorder.reserve(p->cap));
@@ -1730,21 +1802,23 @@ static kg_status derive_lanes(kg_pods* p, const int32_t* set) {
         const int64_t* hc = reinterpret_cast<const int64_t*>(h + L.cols);
         for (int c = 0; c < DEDUP_COLS; c++) rows.col[c] = hc + (size_t)c * n;
         rows.flags = reinterpret_cast<const uint32_t*>(h + L.flags);
-        rows.set = any ? set : nullptr;
+        rows.set = any ? gid : nullptr;
         dedup_rows(rows, n, rp, p->dedup_slots);
         dedup_order(order, n, n_fast, rp, rorder, &n_rep_fast, &n_rep);
     }
-    uint32_t plain = n, plain_fast = n_fast, rplain = n_rep, rplain_fast = n_rep_fast, ns = 0, nrs = 0;
+    uint32_t plain = n, plain_fast = n_fast, rplain = n_rep, rplain_fast = n_rep_fast, ns = 0, nrs = 0, nt = 0, nrt = 0;
     std::vector<uint32_t> sorder, srorder;
     if (any) {
         sorder.resize(n);
-        ns = dedup_split_sets(order, n, n_fast, set, wk, sorder.data(), &plain, &plain_fast);
+        ns = dedup_split_sets(order, n, n_fast, gid, wk, sorder.data(), &plain, &plain_fast);
+        for (uint32_t t = 0; t < ns; t++) nt += has_term(sorder[t]);  // the tail of the list
         if (p->dedup) {
             srorder.resize(n_rep);
-            nrs = dedup_split_sets(rorder, n_rep, n_rep_fast, set, wk, srorder.data(), &rplain, &rplain_fast);
+            nrs = dedup_split_sets(rorder, n_rep, n_rep_fast, gid, wk, srorder.data(), &rplain, &rplain_fast);
+            for (uint32_t t = 0; t < nrs; t++) nrt += has_term(srorder[t]);
         }
     } else {
-        // row -> lane for the one-pod-block select (a batch with sets does not take it)
+        // row -> lane for the one-pod-block select (a batch with sets or terms does not take it)
         if (n <= 256)
             for (uint32_t t = 0; t < n; t++) h[L.lane + order[t]] = (uint8_t)t;
         if (p->dedup && n_rep <= 256) {
@@ -1763,15 +1837,18 @@ static kg_status derive_lanes(kg_pods* p, const int32_t* set) {
         if (nrs) HIP_TRY(ctx, hipMemcpyAsync(p->d_srorder, srorder.data(), sizeof(uint32_t) * nrs, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the set lists are staged in pageable memory
     }
-    p->any_set = any;
+    p->any_set = any_s;
+    p->any_term = any_t;
     p->n_rep = n_rep;
     p->n_rep_fast = n_rep_fast;
     p->n_plain_lanes = plain;
     p->n_plain_fast = plain_fast;
     p->n_rep_plain = rplain;
     p->n_rep_plain_fast = rplain_fast;
-    p->n_set_lanes = ns;
-    p->n_rep_set = nrs;
+    p->n_set_lanes = ns - nt;
+    p->n_rep_set = nrs - nrt;
+    p->n_term_lanes = nt;
+    p->n_rep_term = nrt;
     return KG_OK;
 }
 
@@ -1784,7 +1861,7 @@ kg_status kg_pods_set_node_sets(kg_pods* p, const kg_node_sets* sets) {
         const bool had = p->any_set;
         p->sets_given = p->tab_valid = false;
         p->h_pod_set.clear();
-        return had ? derive_lanes(p, nullptr) : KG_OK;
+        return had ? derive_lanes(p) : KG_OK;
     }
     const uint32_t n = p->n, w32 = sets_words32(sets->n_nodes);
     if (n && !sets->pod_set) return fail(ctx, KG_INVALID_ARG, "null pod_set");
@@ -1815,7 +1892,7 @@ kg_status kg_pods_set_node_sets(kg_pods* p, const kg_node_sets* sets) {
     p->set_n_nodes = sets->n_nodes;
     p->sets_given = true;
     p->tab_valid = false;
-    return derive_lanes(p, p->h_pod_set.data());
+    return derive_lanes(p);
 }
 
 // A batch with candidate node sets against snapshot s: the node counts agree and the record-order table is the one of
@@ -1839,6 +1916,104 @@ static kg_status ensure_sets(kg_snap* s, kg_pods* p) {
 static kg_status refuse_sets(kg_snap* s, kg_pods* p, const char* what) {
     if (!p->any_set) return KG_OK;
     return fail(s->ctx, KG_UNSUPPORTED, "%s with candidate node sets (kg_pods_set_node_sets)", what);
+}
+
+kg_status kg_pods_set_node_scores(kg_pods* p, const kg_node_scores* sc) {
+    if (!p) return KG_INVALID_ARG;
+    kg_ctx* ctx = p->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!p->batch_uploaded) return fail(ctx, KG_INVALID_ARG, "host score terms before kg_pods_upload");
+    if (!sc) {
+        const bool had = p->any_term;
+        p->scores_given = p->any_norm = p->rtab_valid = false;
+        p->h_pod_terms.clear();
+        p->term_bound = 0;
+        return had ? derive_lanes(p) : KG_OK;
+    }
+    const uint32_t n = p->n, rows = sc->n_rows, nn = sc->n_nodes;
+    constexpr uint32_t T = KG_SCORE_TERMS, WMAX = 1u << 20;
+    if (n && !sc->pod_terms) return fail(ctx, KG_INVALID_ARG, "null pod_terms");
+    if (rows && (!sc->mode || !sc->weight)) return fail(ctx, KG_INVALID_ARG, "%u rows without mode / weight", rows);
+    if (rows && nn && !sc->raw) return fail(ctx, KG_INVALID_ARG, "%u rows without raw", rows);
+    if (rows > 65535u) return fail(ctx, KG_INVALID_ARG, "%u rows > 65535", rows);
+    for (size_t x = 0; x < (size_t)n * T; x++)
+        if (sc->pod_terms[x] < -1 || sc->pod_terms[x] >= (int64_t)rows)
+            return fail(ctx, KG_INVALID_ARG, "pod %zu: row %d outside [-1, %u)", x / T, sc->pod_terms[x], rows);
+    std::vector<uint32_t> row_max(rows, 0);
+    for (uint32_t r = 0; r < rows; r++) {
+        if (sc->mode[r] > KG_SCORE_NORMALIZE_REVERSE) return fail(ctx, KG_INVALID_ARG, "row %u: mode %u", r, sc->mode[r]);
+        if (sc->weight[r] > WMAX) return fail(ctx, KG_INVALID_ARG, "row %u: weight %u above 2^20", r, sc->weight[r]);
+        for (uint32_t i = 0; i < nn; i++) {
+            const int32_t v = sc->raw[(size_t)r * nn + i];
+            if (v < 0 || v > KG_SCORE_RAW_MAX)
+                return fail(ctx, KG_INVALID_ARG, "row %u node %u: raw %d outside [0, %d]", r, i, v, KG_SCORE_RAW_MAX);
+            row_max[r] = std::max(row_max[r], (uint32_t)v);
+        }
+    }
+    // the largest per-pod bound of the terms (the evaluating call adds the snapshot's) and whether pass 1 runs
+    uint64_t bound = 0;
+    bool norm = false;
+    for (uint32_t j = 0; j < n; j++) {
+        uint64_t b = 0;
+        for (uint32_t t = 0; t < T; t++) {
+            const int32_t r = sc->pod_terms[(size_t)j * T + t];
+            if (r < 0) continue;
+            b += (uint64_t)sc->weight[r] * (sc->mode[r] == KG_SCORE_RAW ? row_max[r] : 100u);
+            norm |= sc->mode[r] != KG_SCORE_RAW;
+        }
+        bound = std::max(bound, b);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<int32_t> ids(sc->pod_terms, sc->pod_terms + (size_t)n * T);
+    const size_t cells = (size_t)rows * nn;
+    p->rtab_valid = false;  // before a failure can leave d_score_rtab empty
+    HIP_TRY(ctx, grow(ctx, p->d_score_raw, std::max<size_t>(cells, 1)));
+    HIP_TRY(ctx, grow(ctx, p->d_score_rtab, std::max<size_t>(cells, 1)));
+    HIP_TRY(ctx, grow(ctx, p->d_score_mode, std::max<size_t>(rows, 1)));
+    HIP_TRY(ctx, grow(ctx, p->d_score_weight, std::max<size_t>(rows, 1)));
+    HIP_TRY(ctx, p->d_pod_terms.reserve((size_t)p->cap * T));
+    HIP_TRY(ctx, p->d_term_max.reserve((size_t)p->cap * T));
+    // an earlier select of this batch may still read the buffers: the copies are ordered behind it on the main stream
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(p->d_pod_terms, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (cells) HIP_TRY(ctx, hipMemcpyAsync(p->d_score_raw, sc->raw, sizeof(int32_t) * cells, hipMemcpyHostToDevice, ctx->stream));
+    if (rows) {
+        HIP_TRY(ctx, hipMemcpyAsync(p->d_score_mode, sc->mode, sizeof(uint32_t) * rows, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(p->d_score_weight, sc->weight, sizeof(uint32_t) * rows, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // staged in pageable memory
+    p->h_pod_terms.swap(ids);
+    p->score_n_rows = rows;
+    p->score_n_nodes = nn;
+    p->term_bound = bound;
+    p->any_norm = norm;
+    p->scores_given = true;
+    return derive_lanes(p);
+}
+
+// A batch with host score terms against snapshot s (select, verify): the node counts agree, the largest total fits the
+// packed key, and (select: table) the record-order rows are those of this snapshot's current layout, rebuilt as
+// ensure_sets rebuilds its table. No-op for a batch without a descriptor.
+static kg_status ensure_scores(kg_snap* s, kg_pods* p, bool table) {
+    kg_ctx* ctx = s->ctx;
+    if (!p->scores_given) return KG_OK;
+    if (p->score_n_nodes != s->n)
+        return fail(ctx, KG_INVALID_ARG, "host score terms over %u nodes, snapshot of %u", p->score_n_nodes, s->n);
+    const int64_t wsum = (int64_t)s->cfg.weight_nrf + s->cfg.weight_la + s->cfg.weight_numa + s->cfg.weight_dev + s->cfg.weight_rsv;
+    if ((uint64_t)wsum * 100u + p->term_bound >= (1ull << 31))
+        return fail(ctx, KG_INVALID_ARG, "score weights and host score terms too large for the packed key");
+    if (!table || !p->any_term || (p->rtab_valid && p->rtab_uid == s->uid && p->rtab_layout == s->layout)) return KG_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_scores_table(s->d_nodes, s->n, p->scores_dev(), p->d_score_rtab, ctx->stream));
+    p->rtab_valid = true;
+    p->rtab_uid = s->uid;
+    p->rtab_layout = s->layout;
+    return KG_OK;
+}
+
+// Evaluating calls that do not serve a batch with host score terms.
+static kg_status refuse_scores(kg_snap* s, kg_pods* p, const char* what) {
+    if (!p->any_term) return KG_OK;
+    return fail(s->ctx, KG_UNSUPPORTED, "%s with host score terms (kg_pods_set_node_scores)", what);
 }
 
 kg_status kg_pods_destroy(kg_pods* p) {
@@ -1915,9 +2090,12 @@ kg_status kg_eval_verify(kg_snap* s, kg_pods* p, kg_verify_out* out) {
     if (st != KG_OK) return st;
     if (s->ext()) {
         st = refuse_sets(s, p, "verify on a snapshot with config-5 tables");
+        if (st == KG_OK) st = refuse_scores(s, p, "verify on a snapshot with config-5 tables");
         return st != KG_OK ? st : ext_verify(s, p, out);
     }
     st = ensure_sets(s, p);
+    if (st != KG_OK) return st;
+    st = ensure_scores(s, p, false);  // the post-pass reads the rows in snapshot order
     if (st != KG_OK) return st;
     const size_t pairs = (size_t)p->n * s->n;
     if (pairs == 0) return KG_OK;
@@ -1934,6 +2112,8 @@ kg_status kg_eval_verify(kg_snap* s, kg_pods* p, kg_verify_out* out) {
     HIP_TRY(ctx, launch_verify(s->d_nodes, s->d_zones, p->dev, p->n, s->n, s->kcfg, force_exact(), d, ctx->stream));
     // excluded pairs: the output matrix is in snapshot order, like the uploaded bitmap
     if (p->any_set) HIP_TRY(ctx, launch_sets_verify(p->sets_dev(), p->n, s->n, d.status, d.total, ctx->stream));
+    // host score terms: the feasible candidate pairs' totals, over the status words the sets have completed
+    if (p->any_term) HIP_TRY(ctx, launch_scores_verify(p->scores_dev(), p->n, s->n, d.status, d.total, ctx->stream));
     struct {
         void* dst;
         const void* src;
@@ -2764,6 +2944,8 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     if (s->ext()) {
         kg_status st0 = refuse_sets(s, p, "select on a snapshot with config-5 tables");
         if (st0 != KG_OK) return st0;
+        st0 = refuse_scores(s, p, "select on a snapshot with config-5 tables");
+        if (st0 != KG_OK) return st0;
         st0 = check_ext(s);
         if (st0 != KG_OK) return st0;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2806,7 +2988,9 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     {
-        const kg_status sst = ensure_sets(s, p);  // before anything of the batch's result state changes
+        kg_status sst = ensure_sets(s, p);  // before anything of the batch's result state changes
+        if (sst != KG_OK) return sst;
+        sst = ensure_scores(s, p, true);
         if (sst != KG_OK) return sst;
     }
     p->k_last = k;
@@ -2825,8 +3009,8 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     const uint32_t n_lanes = dd ? p->n_rep_plain : p->n_plain_lanes, n_lanes_fast = dd ? p->n_rep_plain_fast : p->n_plain_fast;
     LaunchSelect a = make_select(s, p->dev, dd ? p->d_rorder : p->d_order, n_lanes, n_lanes_fast, p->n, kk, true, d_out,
                                  nullptr, p->d_pstat, &parts);
-    // the one-pod-block select writes every row of out and pstat through the lane tables: not with sets
-    if (!p->any_set && select_small(s, a)) {
+    // the one-pod-block select writes every row of out and pstat through the lane tables: not with sets or terms
+    if (!p->lanes_split() && select_small(s, a)) {
         // one launch (or two) writes every row of d_out and d_pstat: no memset, no side stream, no expansion
         const uint32_t lp = (a.n_fast + 63) / 64 * 64;
         kg_status st;
@@ -2887,8 +3071,8 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         return st;
     }
     HIP_TRY(ctx, hipMemsetAsync(p->d_pstat, 0, sizeof(uint32_t) * p->n, ctx->stream));
-    // the set lanes insert into zeroed rows by atomics, whichever form the other lanes' launch takes
-    if (p->any_set) HIP_TRY(ctx, hipMemsetAsync(d_out, 0, sizeof(uint64_t) * kk * p->n, ctx->stream));
+    // the set and term lanes insert into zeroed rows by atomics, whichever form the other lanes' launch takes
+    if (p->lanes_split()) HIP_TRY(ctx, hipMemsetAsync(d_out, 0, sizeof(uint64_t) * kk * p->n, ctx->stream));
     HIP_TRY(ctx, grow(ctx, p->d_partial, std::max<size_t>((size_t)parts * p->n * kk, 1)));
     kg_status st = KG_OK;
     a.partial = p->d_partial;
@@ -2937,6 +3121,15 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
                                         dd ? p->n_rep_set : p->n_set_lanes, p->sets_dev(), s->n0, s->n, s->base, kk, s->kcfg,
                                         a.exact, !a.exact && !force_int() && s->weights_small, d_out, p->d_pstat,
                                         ctx->stream));
+    // the lanes with a host score term (kg_scores.hip): the tail of the same lists, pass 1 and pass 2 in turn
+    if (p->any_term) {
+        const uint32_t first = dd ? p->n_rep_set : p->n_set_lanes;
+        HIP_TRY(ctx, launch_select_scores(s->d_nodes, s->d_zones, p->dev, (dd ? p->d_srorder : p->d_sorder) + first,
+                                          dd ? p->n_rep_term : p->n_term_lanes, p->any_set ? p->d_pod_set.get() : nullptr,
+                                          p->d_set_tab, sets_words(s->n), p->scores_dev(), p->d_term_max, p->any_norm,
+                                          s->n0, s->n, s->base, kk, s->kcfg, a.exact,
+                                          !a.exact && !force_int() && s->weights_small, d_out, p->d_pstat, ctx->stream));
+    }
     // after the side-stream join: every consumer (kg_result_keys, the all-gather, kg_result_status) sees whole tables
     if (dd) HIP_TRY(ctx, launch_expand_keys(p->d_rep, p->n, kk, d_out, p->d_pstat, ctx->stream));
     return record_end(ctx, e0, e1);
@@ -3269,6 +3462,8 @@ kg_status kg_replay(kg_snap* s, kg_pods* p, int32_t* out_node, int64_t* out_tota
     kg_ctx* ctx = s->ctx;
     std::lock_guard<std::mutex> g(ctx->mu);
     st = check_views(s);
+    if (st != KG_OK) return st;
+    st = refuse_scores(s, p, "replay");  // each cycle's maxima would follow the cycle's feasible set
     if (st != KG_OK) return st;
     if (rsv_numa_batch(s, p))
         return fail(ctx, KG_UNSUPPORTED, "replay over nodes whose reservations hold NUMA / cpuset allocations "
@@ -4397,6 +4592,8 @@ kg_status kg_shard_select(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* out_keys
     kg_ctx* ctx = s->ctx;
     std::lock_guard<std::mutex> g(ctx->mu);
     st = refuse_sets(s, p, "sharded select");  // the shards' exchange does not carry the sets
+    if (st != KG_OK) return st;
+    st = refuse_scores(s, p, "sharded select");  // a normalised term's maximum is global over the shards
     if (st != KG_OK) return st;
     if (!ctx->comm) return fail(ctx, KG_INVALID_ARG, "kg_shard_init not called");
     if (k == 0 || k > (uint32_t)KG_TOPK_MAX) return fail(ctx, KG_INVALID_ARG, "k=%u outside [1, %d]", k, KG_TOPK_MAX);

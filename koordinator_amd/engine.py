@@ -77,6 +77,8 @@ def lib():
     L.kg_pods_select_lanes.restype = st
     L.kg_pods_set_node_sets.argtypes = [vp, P(abi.KgNodeSets)]  # new within ABI 14: resolved here, at load time
     L.kg_pods_set_node_sets.restype = st
+    L.kg_pods_set_node_scores.argtypes = [vp, P(abi.KgNodeScores)]  # new within ABI 14: resolved here, at load time
+    L.kg_pods_set_node_scores.restype = st
     L.kg_pods_destroy.argtypes = [vp]
     L.kg_pods_destroy.restype = st
     L.kg_eval_verify.argtypes = [vp, vp, P(abi.KgVerifyOut)]
@@ -378,6 +380,29 @@ class PodBatch:
 
     def clear_node_sets(self):
         self.ctx.check(self.ctx.L.kg_pods_set_node_sets(self.h, None), "kg_pods_set_node_sets")
+
+    def set_node_scores(self, pod_terms, raw, mode, weight, n_nodes: int):
+        """kg_pods_set_node_scores: pod_terms[j] = up to KG_SCORE_TERMS row ids of pod j (-1: unused slot), raw[row] =
+        the host plugin's score of every snapshot position, mode[row] a KG_SCORE_* and weight[row] the plugin's weight
+        (koordinator_amd.nodescores builds all four). Copied; the next upload() clears the terms."""
+        pod_terms = np.ascontiguousarray(pod_terms, np.int32).reshape(-1, abi.KG_SCORE_TERMS)
+        if len(pod_terms) != self.n:
+            raise ValueError(f"pod_terms has {len(pod_terms)} rows for {self.n} pods")
+        mode = np.ascontiguousarray(mode, np.uint32).reshape(-1)
+        weight = np.ascontiguousarray(weight, np.uint32).reshape(-1)
+        rows, n_nodes = len(mode), int(n_nodes)
+        raw = np.ascontiguousarray(raw, np.int32).reshape(rows, n_nodes)
+        if len(weight) != rows:
+            raise ValueError(f"{len(weight)} weights for {rows} rows")
+        i32p, u32p = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+        sc = abi.KgNodeScores(
+            (pod_terms if self.n else np.zeros(abi.KG_SCORE_TERMS, np.int32)).ctypes.data_as(i32p),
+            raw.ctypes.data_as(i32p) if raw.size else None, mode.ctypes.data_as(u32p) if rows else None,
+            weight.ctypes.data_as(u32p) if rows else None, rows, n_nodes)
+        self.ctx.check(self.ctx.L.kg_pods_set_node_scores(self.h, C.byref(sc)), "kg_pods_set_node_scores")
+
+    def clear_node_scores(self):
+        self.ctx.check(self.ctx.L.kg_pods_set_node_scores(self.h, None), "kg_pods_set_node_scores")
 
     def select_lanes(self):
         """kg_pods_select_lanes: (lanes, fast lanes) the next plain select launches (fewer than n when equal rows share
