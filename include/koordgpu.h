@@ -688,7 +688,13 @@ kg_status kg_pods_destroy(kg_pods* pods);
 kg_status kg_eval_verify(kg_snap* snap, kg_pods* pods, kg_verify_out* out);
 /* Filter + Score + selectHost for every pending pod against the snapshot as it is (matrix mode):
  * per pod the k best packed keys (kg_make_key), descending, 0 = no feasible node. The launch is
- * asynchronous; results stay on the device until kg_result_keys. */
+ * asynchronous; results stay on the device until kg_result_keys. Where the device kept one result per distinct pod row
+ * (the one-launch top-1 select), kg_result_keys and kg_result_status copy those and fill in the rows on the host, through
+ * the row table of the upload that the select ran on; both may be called any number of times, in either order.
+ * Read a result before the batch's next kg_pods_upload: the upload replaces that table, and until the next select on
+ * the batch both calls then fail with KG_INVALID_ARG ("no selection result") rather than serve rows of the old batch
+ * through the new one's table. (A result kept per row is still served after an upload, as before: the first n_pods
+ * rows of the earlier select.) kg_pods_set_node_sets / kg_pods_set_node_scores do not invalidate a result. */
 kg_status kg_eval_select(kg_snap* snap, kg_pods* pods, uint32_t k);
 kg_status kg_result_keys(kg_pods* pods, uint64_t* out_keys /* n_pods * k */);
 /* Per-pod outcome flags of the last kg_eval_select / kg_shard_select (n_pods entries):

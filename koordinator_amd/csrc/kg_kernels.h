@@ -69,6 +69,10 @@ struct LaunchSelect {
     uint32_t small_replicas;  // replicas of the accumulators; they and *sticket are zero before and after every launch
     uint32_t* sticket;        // arrival counter of the launch
     bool small_rows4;         // lane_of, out and pstat are 16-byte aligned: the finisher stores four rows per thread and step
+    // lane form of the result (one launch only): out and pstat are tables of one entry per lane (lanes rounded up to
+    // whole waves), the finisher stores each lane's key and status word once and no row; lane_of and n_rows are not
+    // read. The reader expands the rows through its own copy of the row -> lane table
+    bool small_lanes;
     // optional timing pair of the small select (both set, or neither): the launch binds ev_start to k_select_small's
     // begin and ev_stop to the end of the kernel that finishes the step (hipExtLaunchKernelGGL), instead of the caller
     // recording events around it. Bound only when launch_select returns hipSuccess

@@ -290,11 +290,18 @@ __global__ __launch_bounds__(256) KG_SEL1_ATTR void k_select1(const NodeRec* __r
 // entry time into the begin word (SMALL_BEGIN_WORD: on the ticket's line, zero between launches like every word of
 // that buffer; the maximum of the complements is the complement of the earliest entry), long before the drain and the ticket that
 // publish the accumulators, so they publish it too. The finisher takes the word back to zero with its other exchanges
-// and, once its row stores have completed, adds end - begin to prof[0] and 1 to prof[1]. With prof == nullptr the
+// and, once its result stores (rows or lanes) have completed, adds end - begin to prof[0] and 1 to prof[1]. With prof == nullptr the
 // kernel runs two uniform branches more and nothing else.
 // PH (KG_SMALL_PHASES, a measurement aid; off in every instantiation the library launches by default): prof is set and
 // the launch's own scratch pair, followed by four clock readings per workgroup that thread 0 stores: entry, loops done
-// (after the slices met in LDS), ticket drawn and, the finisher only (else zero), rows stored.
+// (after the slices met in LDS), ticket drawn and, the finisher only (else zero), results stored.
+// form (uniform; acc_r > 0 only): what the finisher stores. SMALL_FORM_ROWS / SMALL_FORM_ROWS4: out / pstat of every
+// row through lane_of, one by one or four at a time (below). SMALL_FORM_LANES: out and pstat are per-lane tables of lp
+// entries and slice 0's thread j < n_lanes stores its lane's key and status word to out[j] / pstat[j]; lane_of and
+// n_rows are not read, the launch's cost does not depend on the row count, and whoever reads the result expands it
+// (kg_result_keys on the host, through the same row -> lane table). One workgroup alone on the chip storing
+// n_rows x 12 bytes was 2 of the finisher's 3.3 us at config 2's 10,000 rows.
+constexpr uint32_t SMALL_FORM_ROWS = 0, SMALL_FORM_ROWS4 = 1, SMALL_FORM_LANES = 2;
 constexpr uint32_t SMALL_ROW_STEPS = 4;  // the finisher's lane words in flight per thread
 template <uint32_t PM, uint32_t WG, bool PH = false>
 __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__ nodes, const ZoneRec* __restrict__ zones,
@@ -306,7 +313,7 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
                                                            uint32_t* __restrict__ ticket,
                                                            const uint8_t* __restrict__ lane_of, uint32_t n_rows,
                                                            uint64_t* __restrict__ out, uint32_t* __restrict__ pstat,
-                                                           uint64_t* __restrict__ prof, uint32_t rows4) {
+                                                           uint64_t* __restrict__ prof, uint32_t form) {
     __shared__ uint64_t lk[WG];
     __shared__ uint2 ls[WG];
     uint64_t ph_entry = 0, ph_loops = 0;
@@ -464,8 +471,16 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
             top = k2 > top ? k2 : top;
         }
         // bit 0 of the status word: KG_ST_UNSUPPORTED when an unsupported pair's bound reaches the best fast key
-        ls[j] = make_uint2(st.y != 0u && st.y > st.x ? KG_ST_UNSUPPORTED : 0u, 0u);
-        lk[j] = top;
+        st.x = st.y != 0u && st.y > st.x ? KG_ST_UNSUPPORTED : 0u;
+        if (form == SMALL_FORM_LANES) {  // uniform: one key and one status word per lane, whatever the row count
+            if (live) {
+                out[j] = top;
+                pstat[j] = st.x;
+            }
+        } else {
+            ls[j] = make_uint2(st.x, 0u);
+            lk[j] = top;
+        }
     }
     __syncthreads();
     // Four rows per thread and step: one 32-bit word of lane_of, then 2 x 16 bytes of keys and 16 bytes of status
@@ -473,8 +488,9 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
     // the loop below). A thread issues the lane words of SMALL_ROW_STEPS steps before its first store, so up to 16
     // rows x the workgroup's threads cost one load round trip; a one-byte load and two stores per thread and 1,024
     // rows made ten load-then-store round trips of 10,000 rows (the stores count on the loads' counter). The rows
-    // past the last multiple of four go one by one.
-    const uint32_t n4 = rows4 ? n_rows / 4u : 0u;
+    // past the last multiple of four go one by one. The lane form has no rows to store.
+    if (form == SMALL_FORM_LANES) n_rows = 0u;
+    const uint32_t n4 = form == SMALL_FORM_ROWS4 ? n_rows / 4u : 0u;
     const uint32_t* const lane4 = reinterpret_cast<const uint32_t*>(lane_of);
     for (uint32_t q0 = threadIdx.x; q0 < n4; q0 += SMALL_ROW_STEPS * blockDim.x) {
         uint32_t w[SMALL_ROW_STEPS];
@@ -500,7 +516,7 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
         out[r] = lk[l];
         pstat[r] = ls[l].x;
     }
-    if (PH || prof) {  // uniform: the bracket ends when every row store of the workgroup has completed
+    if (PH || prof) {  // uniform: the bracket ends when every result store of the workgroup has completed
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -1388,7 +1404,8 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
     if (a.k != 1 || !a.fused || a.n_fast == 0 || a.n_fast != a.n_pods || lp > 256 || nc == 0 || nc > SMALL_MAX_CHUNKS ||
         (r0.n_chunks && (r0.chunk == 0 || r0.chunk > SMALL_MAX_CHUNK)) ||
         (r1.n_chunks && (r1.chunk == 0 || r1.chunk > SMALL_MAX_CHUNK)) || a.small_slices == 0 ||
-        a.small_slices * lp > SMALL_WG || !a.skeys || !a.sub || !a.sfhi || !a.lane_of ||
+        a.small_slices * lp > SMALL_WG || !a.skeys || !a.sub || !a.sfhi || (!a.lane_of && !a.small_lanes) ||
+        (a.small_lanes && !a.small_replicas) || !a.out || !a.pstat ||
         (a.small_replicas && !a.sticket) || (a.prof && (!a.small_replicas || a.ev_start || a.ev_stop)) || (a.phases && !a.prof))
         return hipErrorInvalidValue;
     dim3 grid(1, nc), block(lp * a.small_slices);
@@ -1397,7 +1414,7 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
 #define KG_SMALL_ARGS                                                                                                 \
     a.nodes, a.zones, a.pods, a.n_fast, lp, r0.end, r1.end, r0.chunk, r1.chunk, r1.n_chunks, a.index_base, a.cfg,      \
         a.skeys, a.sub, a.sfhi, a.order, a.small_replicas, a.sticket, a.lane_of, a.n_rows, a.out, a.pstat, a.prof,    \
-        a.small_rows4 ? 1u : 0u
+        a.small_lanes ? SMALL_FORM_LANES : a.small_rows4 ? SMALL_FORM_ROWS4 : SMALL_FORM_ROWS
 #define KG_SMALL_WG(PMV, WGV)                                                                                         \
     do {                                                                                                              \
         if (timed)                                                                                                    \

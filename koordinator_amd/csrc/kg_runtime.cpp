@@ -257,6 +257,25 @@ struct kg_pods {
     uint32_t k_last = 0, kk_last = 0;
     PinnedBuf<uint64_t> h_keys;    // pinned download staging of the keys [cap][KG_TOPK_MAX]
     DevBuf<uint32_t> d_pstat;   // per pod: KG_ST_UNSUPPORTED / KG_ST_QUOTA of the last select (kg_result_status)
+    // Form of the last select's result (set wherever k_last is set). Rows: d_keys [n][kk_last] and d_pstat [n]. Lanes
+    // (res_lanes; the one-launch top-1 select on the batch's own tables, select_local): d_lres holds res_lp keys and,
+    // behind them, res_lp status words, one per lane, and row j takes lane res_lane_of[j]: the host's copy of the row ->
+    // lane table that the select's batch was uploaded with, in h_in. d_keys / d_pstat then hold no result; kg_result_keys
+    // and kg_result_status copy the lane tables into h_lres once per select (res_fetched) and gather on the host. The
+    // next upload rewrites h_in: it drops a lane-form result (result_rows with k_last = 0).
+    // d_lres / h_lres are the last LRES_WORDS words of d_in / h_in, behind every region of pod_layout(cap): no upload
+    // copies that far, and the batch has no allocation more than before.
+    static constexpr uint32_t LRES_LANES = 256, LRES_WORDS = LRES_LANES + LRES_LANES / 2;  // 64-bit words
+    uint64_t* d_lres = nullptr;
+    uint64_t* h_lres = nullptr;
+    bool res_lanes = false, res_fetched = false;
+    uint32_t res_lp = 0;
+    const uint8_t* res_lane_of = nullptr;
+    void result_rows(uint32_t k, uint32_t kk) {
+        k_last = k;
+        kk_last = kk;
+        res_lanes = res_fetched = false;
+    }
     DevBuf<uint32_t> d_reason;  // replay: per pod OR of the filter status bits (kg_replay out_reason)
     // kg_eval_diagnose: the requested rows and their KG_DIAG_SLOTS counters, grown on demand (ensure_diag)
     DevBuf<uint32_t> d_diag_rows;
@@ -1469,7 +1488,9 @@ kg_status kg_pods_create(kg_ctx* ctx, uint32_t capacity, kg_pods** out) {
     p->in_bytes = pod_layout(capacity).total;
     hipSetDevice(ctx->device);
     const size_t cap = capacity, keys = (size_t)KG_TOPK_MAX * cap;
-    const bool ok = !p->d_in.alloc(p->in_bytes) && !p->h_in.alloc(p->in_bytes) && !p->d_keys.alloc(keys) &&
+    // the lane tables of a lane-form result (kg_pods.d_lres / h_lres) lie behind the input regions, 256-byte aligned
+    const size_t lres_at = (p->in_bytes + 255) / 256 * 256, in_alloc = lres_at + sizeof(uint64_t) * kg_pods::LRES_WORDS;
+    const bool ok = !p->d_in.alloc(in_alloc) && !p->h_in.alloc(in_alloc) && !p->d_keys.alloc(keys) &&
                     !p->h_keys.alloc(keys) && !p->d_winners.alloc(cap + 1) && !p->d_step.alloc(64) && !p->d_qst.alloc(cap) &&
                     !p->d_dev_max.alloc(cap) && !p->d_rsv_max.alloc(cap) && !p->d_pref.alloc(cap) &&
                     !p->d_minors.alloc(cap + 1) && !p->d_buckets.alloc(REPLAY_BUCKET_WORDS) && !p->d_aout.alloc(4) &&
@@ -1481,6 +1502,8 @@ kg_status kg_pods_create(kg_ctx* ctx, uint32_t capacity, kg_pods** out) {
         delete p;
         return fail(ctx, KG_OOM, "pod batch of %u", capacity);
     }
+    p->d_lres = reinterpret_cast<uint64_t*>(p->d_in.get() + lres_at);
+    p->h_lres = reinterpret_cast<uint64_t*>(p->h_in.get() + lres_at);
     pod_views(p, 0);
     *out = p;
     return KG_OK;
@@ -1517,6 +1540,9 @@ kg_status kg_pods_upload(kg_pods* p, const kg_pod_columns* cols, uint32_t n) {
         HIP_TRY(ctx, hipEventSynchronize(p->in_copied));
         p->in_pending = false;
     }
+    // a result kept per lane is read through the staging's row -> lane table, which is rewritten from here on: the
+    // result is gone with it (kg_result_keys: "no selection result" until the next select)
+    if (p->res_lanes) p->result_rows(0, 0);
     const PodLayout L = pod_layout(n);
     uint8_t* h = p->h_in;
     int64_t* hc = reinterpret_cast<int64_t*>(h + L.cols);
@@ -1818,7 +1844,9 @@ static kg_status derive_lanes(kg_pods* p) {
             for (uint32_t t = 0; t < nrs; t++) nrt += has_term(srorder[t]);
         }
     } else {
-        // row -> lane for the one-pod-block select (a batch with sets or terms does not take it)
+        // row -> lane for the one-pod-block select (a batch with sets or terms does not take it). These are the values
+        // kg_pods_upload wrote (same rows, no group ids), and the branch above writes neither table: a lane-form
+        // result of an earlier select (kg_pods.res_lane_of) stays readable across a change of sets or terms
         if (n <= 256)
             for (uint32_t t = 0; t < n; t++) h[L.lane + order[t]] = (uint8_t)t;
         if (p->dedup && n_rep <= 256) {
@@ -2802,9 +2830,11 @@ constexpr uint32_t SMALL_MIN_CHUNK = 8, SMALL_FILL_NUM = 63, SMALL_FILL_DEN = 64
 // finisher. KG_SMALL_REPLICAS (read per call) sets the count, also past the row gate: the tool and the tests.
 // Row gate (--rows, profiles/small_fused/rows_breakeven.jsonl; 145 lanes, one launch / two launches): 10,000 rows
 // 0.0180 / 0.0250 ms, 50,000 rows 0.0259 / 0.0248, 200,000 rows 0.0558 / 0.0252: the lone finisher writes n_rows x 12
-// bytes, the break-even interpolates to about 45,000 rows, the one launch is taken up to SMALL_FUSED_MAX_ROWS.
+// bytes, the break-even interpolates to about 45,000 rows, the one launch is taken up to SMALL_FUSED_MAX_ROWS. The gate
+// is the row form's: a result kept per lane (lanes_ok below) stores no row, and its one launch measured 0.0149 / 0.0150 /
+// 0.0151 ms at 10,000 / 50,000 / 200,000 rows (tools/small_reader_ab.py, profiles/small_lanes/reader_ab.jsonl).
 constexpr uint32_t SMALL_REPLICAS = 4, SMALL_FUSED_MAX_ROWS = 32768;
-static bool select_small(const kg_snap* s, LaunchSelect& a) {
+static bool select_small(const kg_snap* s, LaunchSelect& a, bool lanes_ok) {
     if (a.k != 1 || !a.fused || a.n_fast == 0 || a.n_fast != a.n_pods || a.n_fast > 256) return false;
     if (std::getenv("KG_NO_SMALL_SELECT")) return false;
     // F_BIG gate: the F_BIG records run inline on the integer path behind the fast records of the wave that meets
@@ -2851,18 +2881,20 @@ static bool select_small(const kg_snap* s, LaunchSelect& a) {
     a.range[0] = r[0];
     a.range[1] = r[1];
     a.small = true;
-    // The finish inside the launch (small_replicas > 0), unless KG_NO_SMALL_FUSED_FINISH (read per call) or the row
-    // count keeps the two launches: a lone finisher writes all n_rows x 12 bytes.
+    // The finish inside the launch (small_replicas > 0), unless KG_NO_SMALL_FUSED_FINISH (read per call) or, in the row
+    // form, the row count keeps the two launches: a lone finisher writes all n_rows x 12 bytes. The lane form
+    // (lanes_ok: the caller can keep the result per lane) stores no row and takes the one launch at any row count.
     const uint32_t nc = r[0].n_chunks + r[1].n_chunks;
     a.small_replicas = 0;
     if (!std::getenv("KG_NO_SMALL_FUSED_FINISH")) {
-        uint32_t rep = a.n_rows <= SMALL_FUSED_MAX_ROWS ? SMALL_REPLICAS : 0u;
+        uint32_t rep = lanes_ok || a.n_rows <= SMALL_FUSED_MAX_ROWS ? SMALL_REPLICAS : 0u;
         if (const char* e = std::getenv("KG_SMALL_REPLICAS")) {  // also past the row gate
             unsigned v = 0;
             if (std::sscanf(e, "%u", &v) == 1 && v >= 1) rep = v;
         }
         a.small_replicas = std::min(rep, nc);  // more replicas than chunks: one chunk each
     }
+    a.small_lanes = lanes_ok && a.small_replicas != 0;
     return true;
 }
 
@@ -2949,8 +2981,7 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         st0 = check_ext(s);
         if (st0 != KG_OK) return st0;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        p->k_last = k;
-        p->kk_last = kk;
+        p->result_rows(k, kk);
         if (p->n == 0) return KG_OK;
         if (s->n == 0) {
             HIP_TRY(ctx, hipMemsetAsync(d_out, 0, sizeof(uint64_t) * kk * p->n, ctx->stream));
@@ -2993,8 +3024,7 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         sst = ensure_scores(s, p, true);
         if (sst != KG_OK) return sst;
     }
-    p->k_last = k;
-    p->kk_last = kk;
+    p->result_rows(k, kk);
     if (p->n == 0) return KG_OK;
     if (s->n == 0) {
         HIP_TRY(ctx, hipMemsetAsync(p->d_pstat, 0, sizeof(uint32_t) * p->n, ctx->stream));
@@ -3009,9 +3039,14 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     const uint32_t n_lanes = dd ? p->n_rep_plain : p->n_plain_lanes, n_lanes_fast = dd ? p->n_rep_plain_fast : p->n_plain_fast;
     LaunchSelect a = make_select(s, p->dev, dd ? p->d_rorder : p->d_order, n_lanes, n_lanes_fast, p->n, kk, true, d_out,
                                  nullptr, p->d_pstat, &parts);
-    // the one-pod-block select writes every row of out and pstat through the lane tables: not with sets or terms
-    if (!p->lanes_split() && select_small(s, a)) {
-        // one launch (or two) writes every row of d_out and d_pstat: no memset, no side stream, no expansion
+    // the one-pod-block select writes every row of out and pstat through the lane tables: not with sets or terms.
+    // Where only kg_result_keys / kg_result_status read the result (d_out is the batch's own d_keys; a sharded select's
+    // lies in the buffer that the all-gather sends) the one launch keeps it per lane and those two expand the rows on
+    // the host (kg_pods.res_lanes). KG_SMALL_ROW_RESULTS (read per call) keeps the rows: the A/B tool and the tests
+    const bool lanes_ok = d_out == p->d_keys.get() && !std::getenv("KG_SMALL_ROW_RESULTS");
+    if (!p->lanes_split() && select_small(s, a, lanes_ok)) {
+        // one launch (or two) writes every row of d_out and d_pstat, or every lane of d_lres: no memset, no side stream,
+        // no expansion
         const uint32_t lp = (a.n_fast + 63) / 64 * 64;
         kg_status st;
         if (a.small_replicas) {
@@ -3036,6 +3071,10 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         // checked here, and such a launch stores its rows one by one
         const auto aligned16 = [](const void* q) { return reinterpret_cast<uintptr_t>(q) % 16u == 0; };
         a.small_rows4 = aligned16(a.lane_of) && aligned16(d_out) && aligned16(p->d_pstat.get());
+        if (a.small_lanes) {  // lp <= LRES_LANES (select_small: at most 256 lanes)
+            a.out = p->d_lres;
+            a.pstat = reinterpret_cast<uint32_t*>(p->d_lres + lp);
+        }
         // kernel-time bracket (kg_profile_read). One launch: the kernel times itself with the device clock (a.prof; the
         // begin word lies in the batch's accumulator buffer, so sacc_dirty clears it too), the launch is the plain one
         // and the host only counts it, once it succeeded. Two launches, a device without a wall clock
@@ -3065,6 +3104,12 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
                 ctx->ev_live.emplace_back(a.ev_start, a.ev_stop);
             }
             if (st == KG_OK && phases) st = small_phases_write(ctx, phases, nc);
+        }
+        // the batch claims a lane-form result only once its launch is on the stream (result_rows above: rows)
+        if (st == KG_OK && a.small_lanes) {
+            p->res_lanes = true;
+            p->res_lp = lp;
+            p->res_lane_of = p->h_in.get() + (a.lane_of - p->d_in.get());
         }
         // a failed call may have left a launch half done: the accumulators are zeroed again before the next one
         if (st != KG_OK && a.small_replicas) p->sacc_dirty = true;
@@ -3144,12 +3189,32 @@ kg_status kg_eval_select(kg_snap* s, kg_pods* p, uint32_t k) {
     return select_local(s, p, k, p->d_keys);
 }
 
+// A lane-form result (kg_pods.res_lanes) on the host: one copy of the res_lp keys and status words into the pinned
+// staging and the stream sync of every result read; the staging then serves every further read of the same select.
+static kg_status fetch_lanes(kg_pods* p) {
+    kg_ctx* ctx = p->ctx;
+    if (!p->res_fetched)
+        HIP_TRY(ctx, hipMemcpyAsync(p->h_lres, p->d_lres, (sizeof(uint64_t) + sizeof(uint32_t)) * p->res_lp,
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    p->res_fetched = true;
+    return KG_OK;
+}
+
 kg_status kg_result_keys(kg_pods* p, uint64_t* out) {
     if (!p || !out) return KG_INVALID_ARG;
     kg_ctx* ctx = p->ctx;
     std::lock_guard<std::mutex> g(ctx->mu);
     if (p->k_last == 0) return fail(ctx, KG_INVALID_ARG, "no selection result");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (p->res_lanes) {  // k_last == kk_last == 1; every table entry is a lane below res_lp
+        kg_status st = fetch_lanes(p);
+        if (st != KG_OK) return st;
+        const uint64_t* lk = p->h_lres;
+        const uint8_t* lane = p->res_lane_of;
+        for (uint32_t j = 0; j < p->n; j++) out[j] = lk[lane[j]];
+        return KG_OK;
+    }
     const uint64_t* h = p->h_keys;  // pinned staging
     HIP_TRY(ctx, hipMemcpyAsync(p->h_keys, p->d_keys, sizeof(uint64_t) * p->kk_last * p->n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -3184,6 +3249,14 @@ kg_status kg_result_status(kg_pods* p, uint32_t* out) {
     std::lock_guard<std::mutex> g(ctx->mu);
     if (p->k_last == 0) return fail(ctx, KG_INVALID_ARG, "no selection result");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (p->res_lanes) {
+        kg_status st = fetch_lanes(p);
+        if (st != KG_OK) return st;
+        const uint32_t* ls = reinterpret_cast<const uint32_t*>(p->h_lres + p->res_lp);
+        const uint8_t* lane = p->res_lane_of;
+        for (uint32_t j = 0; j < p->n; j++) out[j] = ls[lane[j]];
+        return KG_OK;
+    }
     if (p->n) HIP_TRY(ctx, hipMemcpyAsync(out, p->d_pstat, sizeof(uint32_t) * p->n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return KG_OK;
@@ -4610,8 +4683,7 @@ kg_status kg_shard_select(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* out_keys
         // all-reduce per statistic between the two passes (a real exchange step)
         st = check_ext(s);
         if (st != KG_OK) return st;
-        p->k_last = k;
-        p->kk_last = kk;
+        p->result_rows(k, kk);
         if (n == 0) return KG_OK;
         hipEvent_t e0, e1;  // bracket: the whole shard step (its all-reduces included)
         st = record_begin(ctx, &e0, &e1);
@@ -4644,8 +4716,7 @@ kg_status kg_shard_select(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* out_keys
     // exchange the per-shard top-kk keys (8 B x kk per pod per shard) and run the same global selectHost
     NCCL_TRY(ctx, ncclAllGather(local, p->d_gather, (size_t)n * kk, ncclUint64, ctx->comm, ctx->stream));
     HIP_TRY(ctx, launch_merge(p->d_gather, (uint32_t)ctx->world, n, kk, p->d_keys, ctx->stream));
-    p->k_last = k;
-    p->kk_last = kk;
+    p->result_rows(k, kk);
     if (out_keys) {
         std::vector<uint64_t> h((size_t)n * kk);
         HIP_TRY(ctx, hipMemcpyAsync(h.data(), p->d_keys, sizeof(uint64_t) * n * kk, hipMemcpyDeviceToHost, ctx->stream));
