@@ -757,6 +757,35 @@ kg_status kg_eval_diagnose(kg_snap* snap, kg_pods* pods, const uint32_t* rows, u
  * zeros to out_count. The symbol is new within ABI 14: a binding resolves it at load time. */
 kg_status kg_eval_feasible(kg_snap* snap, kg_pods* pods, const uint32_t* rows, uint32_t n_rows, uint32_t fail_mask,
                            uint32_t* out_bits /* n_rows * ((n_nodes + 31) / 32) */, uint32_t* out_count /* n_rows */);
+/* Node offer slots of a gang: per node of this snapshot, how many of the job's pods fit when they are added to the
+ * node one after another (calculateNodeOfferSlot, coscheduling/core/network_topology_solver.go:113-158), the first and
+ * only expensive step of the network-topology planner (PlacePods, :53-111): the caller sums the counts up its topology
+ * tree and deals the pods out on the host. Per node, independently of every other node:
+ *     slot = 0; for t in 0..n_rows-1: Filter(pod rows[t], node with the first t pods added) fails ? stop : add, slot++
+ * "add" is NodeInfo.AddPodInfo: the node's requested cpu / memory / ephemeral-storage / scalars, its non-zero requested
+ * cpu / memory and its pod count grow by the pod's (the req_*, sc_req*, nz_* and num_pods columns). The LoadAware
+ * bases, NUMA zone usage, cpusets and GPU minors stay the snapshot's: LoadAware has no AddPod hook, NodeNUMAResource's
+ * and DeviceShare's return early for a pod that holds no allocation on the node. This is not the Reserve of kg_assume
+ * / kg_replay, and not kg_eval_feasible's evaluation of every pod on the snapshot as it stands.
+ *   rows     batch indices of the job's pods in planner order (extension.SortPodsByIndex); repeats allowed (a gang of
+ *            identical pods may be uploaded once); NULL: every pod in batch order (n_rows must equal the batch size).
+ *   out_slots[i], i the node's snapshot position (index_base is not added): the number of leading pods of rows that
+ *            pass, 0..n_rows.
+ *   out_status[i] (may be NULL): 0 when all n_rows pods passed, else the status word of the pair (rows[out_slots[i]],
+ *            node i) on the node with the first out_slots[i] pods added: bit for bit the word kg_eval_verify reports
+ *            on a snapshot whose columns above were raised by those pods, every failing plugin's bits. A node that
+ *            stops on a word with KG_ST_UNSUPPORTED has a lower-bound count: the caller runs the reference loop there.
+ * Candidate node sets of the batch are honoured, as every Filter of the host's runs in the reference's loop: a pod
+ * whose set excludes the node stops the node with its usual word | KG_ST_NODE_EXCLUDED. Host score terms are ignored
+ * (Filter only). Per-node results do not depend on other nodes: the outputs of node shards concatenate.
+ * Synchronous like kg_eval_diagnose, with its precondition checks in its order. It changes no state of the snapshot
+ * (nor its generation), the batch's keys or kg_result_status. KG_INVALID_ARG: out_slots == NULL with n_nodes > 0, a row
+ * >= the batch size, rows == NULL with another n_rows, candidate node sets over another node count. n_rows == 0 writes
+ * zeros to both outputs; a snapshot of 0 nodes writes nothing. KG_UNSUPPORTED: a snapshot with config-5 tables
+ * (KG_PLUGIN_EXT): Reservation's AddPod (reservation/plugin.go:254-284) moves state its Filter reads, which the
+ * device does not follow. The symbol is new within ABI 14: a binding resolves it at load time. */
+kg_status kg_eval_offer_slots(kg_snap* snap, kg_pods* pods, const uint32_t* rows, uint32_t n_rows,
+                              uint32_t* out_slots /* n_nodes */, uint32_t* out_status /* n_nodes, may be NULL */);
 /* Sequential scheduling of pods[0..n) one at a time with Assume applied on the device between pods
  * (the reference's one-pod-per-cycle semantics). out_node[i] = global node index or -1 (no feasible node,
  * or the selected node's Reserve failed: KG_ST_NUMA_INSUF_* in out_reason).

@@ -146,6 +146,9 @@ KG_BATCH_ASSUMED, KG_BATCH_FAILED, KG_BATCH_SIBLING, KG_BATCH_ROLLED_BACK, KG_BA
 _p64 = C.POINTER(C.c_int64)
 _pu32 = C.POINTER(C.c_uint32)
 
+# kg_eval_offer_slots(snap, pods, rows, n_rows, out_slots, out_status): the prototype of include/koordgpu.h
+KG_EVAL_OFFER_SLOTS_ARGTYPES = [C.c_void_p, C.c_void_p, _pu32, C.c_uint32, _pu32, _pu32]
+
 
 class KgNodeSets(C.Structure):
     """kg_node_sets: per-pod candidate node sets (koordinator_amd.nodesets builds the arrays)."""

@@ -8,10 +8,14 @@ Reference behaviour mirrored here (names, argument meaning, status codes and mes
   BatchScheduler.BatchSchedule                         batch/batch_scheduler.go:74-185
   Engine.RunSchedulingCycle, ValidateAndGroupByRequest batch/engine.go:92-294,348-371
   JobResult.ExampleMessage                             batch/framework/types.go:275-341
+  the network-topology planner (PlacePods)             coscheduling/core/network_topology_solver.go:53-418
 
 `ReplayPlanner.find_one_node` places every pending member of the job with the sequential replay kernel
 (one pod per cycle, Reserve applied on the device between pods) on the live snapshot and rolls the snapshot
 back afterwards (kg_snapshot_checkpoint / kg_snapshot_rollback), so a plan costs no copy of the cluster.
+`TopologyPlanner.find_one_node` plans a gang with a network-topology requirement as the reference does: the
+per-node offer slots come from the device in one call (kg_eval_offer_slots), `place_pods` then sums them up the
+topology tree, picks the lowest topology node under the must-gather layer that holds the job and deals the pods out.
 `BatchScheduler.batch_schedule` then runs the inline batch cycle of the plan on the device
 (kg_batch_schedule): per planned node, in pod-name order, PreFilter + Filter on that node and Reserve; on any
 failure every assumed pod is undone (CleanupAssumedPods) and the job status carries the reference's
@@ -20,6 +24,7 @@ numbers all come from the HIP kernels behind include/koordgpu.h (no CPU fallback
 """
 from __future__ import annotations
 
+import functools
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -141,6 +146,297 @@ class ReplayPlanner:
         plan = BatchScheduleResult(ordered, {p.key: self.node_names[node[t] - self.snap.index_base]
                                              for t, p in enumerate(ordered)})
         return plan, Status(SUCCESS), why
+
+
+# ---- the network-topology planner: node offer slots on the device, the topology solver on the host ----------------------
+# A restatement of coscheduling/core/network_topology_solver.go:53-111 (PlacePods) and :187-418. The reference keeps a
+# TreeNode's children in a Go map and sorts wherever the order matters; here children are walked in name order, so the
+# result does not depend on the order they were inserted in.
+
+NODE_TOPOLOGY_LAYER = "NodeTopologyLayer"  # apis/scheduling/v1alpha1/cluster_network_topology_types.go:29
+# network_topology_solver.go:22 MessageNoCandidateTopologyNodes
+MESSAGE_NO_CANDIDATE_TOPOLOGY_NODES = ("no candidate topology nodes can accommodate job, desiredOfferSlot: {slot}, "
+                                       "{nodes}, {fit}")
+# the framework stops at a node's first failing plugin: the groups of KG_DIAG_FIRST_PLUGIN (include/koordgpu.h)
+_FIRST_PLUGIN_GROUPS = (abi.KG_ST_QUOTA, abi.KG_ST_NODE_EXCLUDED, abi.KG_ST_NRF_MASK, abi.KG_ST_LA_MASK,
+                        abi.KG_ST_NUMA_MASK | abi.KG_ST_UNSUPPORTED, abi.KG_ST_DEV_MASK | abi.KG_ST_DEV_RSV,
+                        abi.KG_ST_RSV_MASK)
+
+
+@dataclass(eq=False)
+class TopologyNode:
+    """networktopology.TreeNode (frameworkext/networktopology/tree.go:93-106). The leaves are NODE_TOPOLOGY_LAYER nodes
+    named by node name."""
+    layer: str
+    name: str
+    parent: Optional["TopologyNode"] = None
+    children: Dict[str, "TopologyNode"] = field(default_factory=dict)
+    offer_slot: int = 0
+    score: int = 0
+    existing_pod_num: int = 0
+
+    def add_child(self, child: "TopologyNode") -> "TopologyNode":
+        child.parent = self
+        self.children[child.name] = child
+        return child
+
+    def sorted_children(self) -> List["TopologyNode"]:
+        return [self.children[k] for k in sorted(self.children) if self.children[k] is not None]
+
+
+@dataclass
+class JobTopologyRequirements:
+    """coscheduling/core/network_topology_types.go:33-40."""
+    must_gather_layer: str = ""
+    desired_offer_slot: int = 0
+    layer_pod_count_multiple: Dict[str, int] = field(default_factory=dict)
+
+
+def copy_topology(root: TopologyNode, parent: Optional[TopologyNode] = None) -> TopologyNode:
+    """The tree's shape with every offer slot, score and existing pod count at zero (what place_pods evaluates on)."""
+    node = TopologyNode(root.layer, root.name, parent)
+    for child in root.sorted_children():
+        node.children[child.name] = copy_topology(child, node)
+    return node
+
+
+def enumerate_node_topology_nodes(root: TopologyNode) -> Dict[str, TopologyNode]:
+    """network_topology_solver.go:187-210 enumerateNodeTopologyNode: node name -> its leaf."""
+    leaves: Dict[str, TopologyNode] = {}
+    layer = [root]
+    while layer:
+        nxt: List[TopologyNode] = []
+        for node in layer:
+            if node.layer == NODE_TOPOLOGY_LAYER:
+                leaves[node.name] = node
+            else:
+                nxt.extend(node.sorted_children())
+        layer = nxt
+    return leaves
+
+
+def evaluate_topology_node(leaves: Dict[str, TopologyNode], node_offer_slot, node_to_score=None,
+                           existing_pod_num=None) -> None:
+    """network_topology_solver.go:212-233 evaluateTopologyNode: every node's numbers are added to its leaf and to each
+    ancestor. A node without a leaf in the tree is left out."""
+    node_to_score = node_to_score or {}
+    for name, slot in node_offer_slot.items():
+        node = leaves.get(name)
+        while node is not None:
+            node.offer_slot += int(slot)
+            node.score += int(node_to_score.get(name, 0))
+            node = node.parent
+    for name, num in (existing_pod_num or {}).items():
+        node = leaves.get(name)
+        while node is not None:
+            node.existing_pod_num += int(num)
+            node = node.parent
+
+
+def constrain_offer_slot_by_pod_count_multiple(root: TopologyNode, layer_pod_count_multiple) -> None:
+    """network_topology_solver.go:239-270: bottom-up, a node's offer slot becomes the sum of its children's constrained
+    slots, rounded down to its layer's multiple."""
+    if not layer_pod_count_multiple:
+        return
+
+    def walk(node: TopologyNode) -> None:
+        if node.layer != NODE_TOPOLOGY_LAYER:
+            for child in node.sorted_children():
+                walk(child)
+            node.offer_slot = sum(child.offer_slot for child in node.sorted_children())
+        multiple = layer_pod_count_multiple.get(node.layer, 0)
+        if multiple > 1:
+            node.offer_slot = node.offer_slot // multiple * multiple
+
+    walk(root)
+
+
+def search_must_gather_satisfied_nodes(requirements: JobTopologyRequirements, root: TopologyNode) -> List[TopologyNode]:
+    """network_topology_solver.go:272-301: the topology nodes of the must-gather layer (the root without one)."""
+    if not requirements.must_gather_layer:
+        return [root]
+    found: List[TopologyNode] = []
+    layer = [root]
+    while not found and layer:
+        nxt: List[TopologyNode] = []
+        for node in layer:
+            if node.layer == requirements.must_gather_layer:
+                found.append(node)
+            else:
+                nxt.extend(node.sorted_children())
+        layer = nxt
+    return found
+
+
+def search_offer_slot_satisfied_nodes(requirements: JobTopologyRequirements,
+                                      must_gathered: Sequence[TopologyNode]) -> List[TopologyNode]:
+    """network_topology_solver.go:303-332: the lowest layer below the must-gather nodes that still has a topology node
+    holding the job; its holding nodes."""
+    candidates: List[TopologyNode] = []
+    layer = list(must_gathered)
+    while layer:
+        nxt: List[TopologyNode] = []
+        holding = [node for node in layer if node.offer_slot >= requirements.desired_offer_slot]
+        for node in holding:
+            nxt.extend(node.sorted_children())
+        if holding:
+            candidates = holding
+        layer = nxt
+    return candidates
+
+
+def topology_node_less(a: TopologyNode, b: TopologyNode, lower_offer_slot: bool) -> bool:
+    """network_topology_solver.go:334-351 topologyNodeLessFunc: more existing pods first, layer by layer upwards; then
+    the offer slots layer by layer (fewer first when lower_offer_slot); then the higher score; then the name."""
+    x, y = a, b
+    while x is not None and y is not None:
+        if x.existing_pod_num != y.existing_pod_num:
+            return x.existing_pod_num > y.existing_pod_num
+        x, y = x.parent, y.parent
+    x, y = a, b
+    while x is not None and y is not None:
+        if x.offer_slot != y.offer_slot:
+            return (x.offer_slot < y.offer_slot) == lower_offer_slot
+        x, y = x.parent, y.parent
+    if a.score != b.score:
+        return a.score > b.score
+    return a.name < b.name
+
+
+def sort_topology_nodes(nodes: Sequence[TopologyNode], lower_offer_slot: bool) -> List[TopologyNode]:
+    def cmp(a, b):
+        return -1 if topology_node_less(a, b, lower_offer_slot) else (1 if topology_node_less(b, a, lower_offer_slot) else 0)
+    return sorted(nodes, key=functools.cmp_to_key(cmp))
+
+
+def distribute_offer_slot(desired_offer_slot: int, node: TopologyNode, distribution: Dict[str, int],
+                          layer_pod_count_multiple=None) -> Tuple[List[str], int]:
+    """network_topology_solver.go:353-393 distributeOfferSlot: (node names in topology order, slots dealt). Children are
+    served largest first, each layer's share rounded down to its multiple."""
+    multiples = layer_pod_count_multiple or {}
+    max_slot = min(node.offer_slot, desired_offer_slot)
+    multiple = multiples.get(node.layer, 0)
+    if multiple > 1:
+        max_slot = max_slot // multiple * multiple
+    if node.layer == NODE_TOPOLOGY_LAYER:
+        distribution[node.name] = max_slot
+        return [node.name], max_slot
+    ordered: List[str] = []
+    dealt, remaining = 0, max_slot
+    for child in sort_topology_nodes(node.sorted_children(), False):
+        names, got = distribute_offer_slot(remaining, child, distribution, multiples)
+        ordered.extend(names)
+        remaining -= got
+        dealt += got
+    return ordered, dealt
+
+
+def distribute_pods(pods: Sequence[JobPod], ordered_nodes: Sequence[str], node_to_offer_slot: Dict[str, int]
+                    ) -> Dict[str, str]:
+    """network_topology_solver.go:395-418 distributePods: the pods by name over the nodes in topology order."""
+    left = dict(node_to_offer_slot)
+    pod_to_node: Dict[str, str] = {}
+    at = 0
+    for p in sorted(pods, key=lambda q: q.name):
+        while at < len(ordered_nodes) and left.get(ordered_nodes[at], 0) <= 0:
+            at += 1
+        if at == len(ordered_nodes):
+            raise ValueError(f"{len(pods)} pods over {sum(max(v, 0) for v in node_to_offer_slot.values())} dealt slots")
+        pod_to_node[p.key] = ordered_nodes[at]
+        left[ordered_nodes[at]] -= 1
+    return pod_to_node
+
+
+def first_plugin_word(word: int) -> int:
+    """A status word masked to its first non-empty plugin group (KG_DIAG_FIRST_PLUGIN's order)."""
+    for group in _FIRST_PLUGIN_GROUPS:
+        if word & group:
+            return word & group
+    return 0
+
+
+def first_plugin_counts(words) -> np.ndarray:
+    """The row of first-plugin reason counts (engine.eval_diagnose's format, reasons.fit_error's input) of the given
+    nodes' status words; zero words count as feasible."""
+    row = np.zeros(abi.KG_DIAG_SLOTS, np.uint32)
+    for w in words:
+        w = first_plugin_word(int(w))
+        if w == 0:
+            row[abi.KG_DIAG_FEASIBLE] += 1
+            continue
+        for b in range(32):
+            if (w >> b) & 1:
+                row[b] += 1
+        if w & abi.KG_ST_DEV_MASK:
+            row[abi.KG_DIAG_DEV_CODE0 + abi.dev_code(w)] += 1
+    return row
+
+
+def place_pods(root: TopologyNode, node_offer_slot, requirements: JobTopologyRequirements, pods: Sequence[JobPod],
+               existing_pod_num=None, node_to_score=None, node_status=None, num_all_nodes: Optional[int] = None
+               ) -> Tuple[Optional[Dict[str, str]], str]:
+    """network_topology_solver.go:53-111 PlacePods after its first step: node_offer_slot {node name: count} (the
+    device's, kg_eval_offer_slots) summed up the tree, the lowest topology node under the must-gather layer that holds
+    desired_offer_slot pods, the pods dealt out over its nodes. -> ({pod key: node name}, "") or (None, the reference's
+    MessageNoCandidateTopologyNodes text). node_status {node name: status word of the first pod that failed there}
+    makes the FitError part of the message, over num_all_nodes nodes (default: the nodes given). Works on its own copy
+    of the tree: a pure function of its arguments."""
+    tree = copy_topology(root)
+    evaluate_topology_node(enumerate_node_topology_nodes(tree), node_offer_slot, node_to_score, existing_pod_num)
+    constrain_offer_slot_by_pod_count_multiple(tree, requirements.layer_pod_count_multiple)
+    must_gathered = search_must_gather_satisfied_nodes(requirements, tree)
+    candidates = search_offer_slot_satisfied_nodes(requirements, must_gathered)
+    for candidate in sort_topology_nodes(candidates, True):
+        distribution: Dict[str, int] = {}
+        ordered, actual = distribute_offer_slot(requirements.desired_offer_slot, candidate, distribution,
+                                                requirements.layer_pod_count_multiple)
+        if actual >= requirements.desired_offer_slot:
+            return distribute_pods(pods, ordered, distribution), ""
+    listed = sorted(f"topology topologyNode {n.layer}/{n.name}: {n.offer_slot}" for n in must_gathered)
+    words = [w for w in (node_status or {}).values() if int(w)]
+    n_all = len(node_offer_slot) if num_all_nodes is None else int(num_all_nodes)
+    msg = MESSAGE_NO_CANDIDATE_TOPOLOGY_NODES.format(slot=requirements.desired_offer_slot, nodes=";".join(listed),
+                                                     fit=reasons.fit_error(first_plugin_counts(words), n_all))
+    if requirements.layer_pod_count_multiple:
+        msg += "; podCountMultiple constraints: " + ", ".join(
+            sorted(f"{layer}={m}" for layer, m in requirements.layer_pod_count_multiple.items()))
+    return None, msg
+
+
+class TopologyPlanner:
+    """FindOneNodePlugin for a gang with a network-topology requirement (network_topology_workflow.go:70-160): the
+    per-node offer slots come from the device in one call (kg_eval_offer_slots), the topology solver runs on the host
+    (place_pods). Plain snapshots only; a node whose count stopped on KG_ST_UNSUPPORTED offers a lower bound."""
+
+    name = "KoordGPUTopologyPlanner"
+
+    def __init__(self, snap: engine.Snapshot, node_names: Sequence[str], root: TopologyNode):
+        self.snap = snap
+        self.node_names = list(node_names)
+        self.root = root
+
+    def find_one_node(self, members: Sequence[JobPod], table: abi.Table, requirements: JobTopologyRequirements,
+                      existing_pod_num=None, node_to_score=None
+                      ) -> Tuple[Optional[BatchScheduleResult], Status, Optional[np.ndarray]]:
+        """Plan for all pending members (rows of `table` in `members` order) -> (plan, status, offer slots per node of
+        the snapshot). Skip when there is no job, Unschedulable with the solver's message when no topology node under
+        the must-gather layer holds the job."""
+        if len(members) == 0:
+            return None, Status(SKIP), None
+        order = sort_pods_by_index(range(len(members)), members)
+        pods = engine.PodBatch(self.snap.ctx, abi.take(table, np.asarray(order, np.int64)))
+        try:
+            slots, words = engine.eval_offer_slots(self.snap, pods, status=True)
+        finally:
+            pods.close()
+        ordered = [members[i] for i in order]
+        offer = {name: int(slots[i]) for i, name in enumerate(self.node_names)}
+        stopped = {name: int(words[i]) for i, name in enumerate(self.node_names) if words[i]}
+        pod_to_node, msg = place_pods(self.root, offer, requirements, ordered, existing_pod_num, node_to_score,
+                                      node_status=stopped, num_all_nodes=len(self.node_names))
+        if pod_to_node is None:
+            return None, Status(UNSCHEDULABLE, msg), slots
+        return BatchScheduleResult(ordered, pod_to_node), Status(SUCCESS), slots
 
 
 @dataclass

@@ -38,6 +38,7 @@
 #include "kg_layout.h"
 #include "kg_scores.h"
 #include "kg_sets.h"
+#include "kg_slots.h"
 
 using namespace kg;
 
@@ -287,6 +288,10 @@ struct kg_pods {
     DevBuf<uint64_t> d_feas_rtab;
     DevBuf<uint32_t> d_feas_out;
     DevBuf<uint32_t> d_feas_count;
+    // kg_eval_offer_slots: the requested rows and the [2][n_nodes] counts and status words in snapshot order, grown on
+    // demand (ensure_slots)
+    DevBuf<uint32_t> d_slot_rows;
+    DevBuf<uint32_t> d_slot_out;
     DevBuf<DevSum> d_devsum;    // per record DevSum of the last config-5 select
     DevBuf<uint64_t> d_gz;      // gpu_zone_sum per (class-1 record, GPU request class) of the last config-5 select
     DevBuf<uint8_t> d_rcode;    // [kg_rsv_dev table][DEV_CLASSES]: GPU allocator outcome on the restore tables
@@ -2283,6 +2288,65 @@ kg_status kg_eval_feasible(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_
                                 hipMemcpyDeviceToHost, ctx->stream));
     if (out_count)
         HIP_TRY(ctx, hipMemcpyAsync(out_count, p->d_feas_count, sizeof(uint32_t) * n_rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KG_OK;
+}
+
+// Scratch of kg_eval_offer_slots for n_rows requested rows over n_nodes nodes: no allocation on the steady path.
+static kg_status ensure_slots(kg_pods* p, size_t n_rows, uint32_t n_nodes) {
+    kg_ctx* ctx = p->ctx;
+    HIP_TRY(ctx, grow(ctx, p->d_slot_rows, std::max<size_t>(n_rows, 64)));
+    HIP_TRY(ctx, grow(ctx, p->d_slot_out, 2 * std::max<size_t>(n_nodes, 64)));
+    return KG_OK;
+}
+
+kg_status kg_eval_offer_slots(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_t n_rows, uint32_t* out_slots,
+                              uint32_t* out_status) {
+    kg_status st = check_pair(s, p);
+    if (st != KG_OK) return st;
+    kg_ctx* ctx = s->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!rows && n_rows != p->n)
+        return fail(ctx, KG_INVALID_ARG, "rows == NULL with n_rows %u != batch size %u", n_rows, p->n);
+    if (rows)
+        for (uint32_t t = 0; t < n_rows; t++)
+            if (rows[t] >= p->n) return fail(ctx, KG_INVALID_ARG, "rows[%u] = %u >= batch size %u", t, rows[t], p->n);
+    if (!out_slots && s->n) return fail(ctx, KG_INVALID_ARG, "null slots output");
+    st = check_views(s);
+    if (st != KG_OK) return st;
+    if (s->ext())  // Reservation's AddPod moves state its Filter reads (reservation/plugin.go:254-284)
+        return fail(ctx, KG_UNSUPPORTED, "offer slots on a snapshot with config-5 tables");
+    st = ensure_sets(s, p);
+    if (st != KG_OK) return st;
+    if (s->n == 0) return KG_OK;
+    if (n_rows == 0) {
+        std::memset(out_slots, 0, sizeof(uint32_t) * s->n);
+        if (out_status) std::memset(out_status, 0, sizeof(uint32_t) * s->n);
+        return KG_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = ensure_slots(p, n_rows, s->n);
+    if (st != KG_OK) return st;
+    if (rows)
+        HIP_TRY(ctx, hipMemcpyAsync(p->d_slot_rows, rows, sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice, ctx->stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    st = record_begin(ctx, &e0, &e1);
+    if (st != KG_OK) return st;
+    uint32_t* d_slots = p->d_slot_out;
+    uint32_t* d_status = d_slots + s->n;
+    const hipError_t le = launch_offer_slots(s->d_nodes, s->d_zones, p->dev, rows ? p->d_slot_rows : nullptr, n_rows, s->n,
+                                             s->kcfg, force_exact(), d_slots, d_status, ctx->stream,
+                                             p->any_set ? p->d_pod_set : nullptr, p->d_set_tab, sets_words(s->n));
+    if (le != hipSuccess) {
+        bracket_drop(ctx, e0, e1);
+        return fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR, "kg_eval_offer_slots: %s",
+                    hipGetErrorString(le));
+    }
+    st = record_end(ctx, e0, e1);
+    if (st != KG_OK) return st;
+    HIP_TRY(ctx, hipMemcpyAsync(out_slots, d_slots, sizeof(uint32_t) * s->n, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_status)
+        HIP_TRY(ctx, hipMemcpyAsync(out_status, d_status, sizeof(uint32_t) * s->n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return KG_OK;
 }

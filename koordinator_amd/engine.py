@@ -87,6 +87,8 @@ def lib():
     L.kg_eval_diagnose.restype = st
     L.kg_eval_feasible.argtypes = [vp, vp, P(u32), u32, u32, P(u32), P(u32)]  # new within ABI 14: resolved at load time
     L.kg_eval_feasible.restype = st
+    L.kg_eval_offer_slots.argtypes = abi.KG_EVAL_OFFER_SLOTS_ARGTYPES  # new within ABI 14: resolved at load time
+    L.kg_eval_offer_slots.restype = st
     L.kg_eval_select.argtypes = [vp, vp, u32]
     L.kg_eval_select.restype = st
     L.kg_result_keys.argtypes = [vp, P(u64)]
@@ -476,6 +478,25 @@ def eval_feasible(snap: Snapshot, pods: PodBatch, rows=None, fail_mask: int = 0x
     snap.ctx.check(snap.ctx.L.kg_eval_feasible(snap.h, pods.h, rp, n_rows, int(fail_mask) & 0xFFFFFFFF, op,
                                                cnt.ctypes.data_as(P) if counts else None), "kg_eval_feasible")
     return (out, cnt[:n_rows]) if counts else out
+
+
+def eval_offer_slots(snap: Snapshot, pods: PodBatch, rows=None, status: bool = False):
+    """kg_eval_offer_slots: uint32[n_nodes], per node (snapshot position) how many leading pods of `rows` (batch indices
+    in planner order, repeats allowed; None = every pod in batch order) fit when added to the node one after another
+    (calculateNodeOfferSlot). status: also return uint32[n_nodes], 0 where every pod passed, else the status word of
+    the first pod that did not, on the node with the pods before it added."""
+    P = C.POINTER(C.c_uint32)
+    if rows is None:
+        n_rows, rp = pods.n, None
+    else:
+        rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        n_rows = len(rows)
+        rp = (rows if n_rows else np.zeros(1, np.uint32)).ctypes.data_as(P)  # an empty list is not "every pod"
+    slots = np.zeros(max(snap.n, 1), np.uint32)
+    word = np.zeros(max(snap.n, 1), np.uint32)
+    snap.ctx.check(snap.ctx.L.kg_eval_offer_slots(snap.h, pods.h, rp, n_rows, slots.ctypes.data_as(P),
+                                                  word.ctypes.data_as(P) if status else None), "kg_eval_offer_slots")
+    return (slots[:snap.n], word[:snap.n]) if status else slots[:snap.n]
 
 
 def eval_select_async(snap: Snapshot, pods: PodBatch, k: int = 1):
