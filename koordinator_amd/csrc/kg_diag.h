@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
-#include "kg_kernels.h"
+#include "kg_rowfilter.h"
 
 namespace kg {
 
@@ -25,13 +25,8 @@ inline uint32_t diag_chunk(uint32_t n_nodes, uint32_t n_rows, uint32_t block, ui
 }
 
 // Reason node counts of the requested rows (kg_eval_diagnose): counts[t][KG_DIAG_SLOTS] += the histogram of the
-// counted status words of pod rows[t] (nullptr: pod t) over every record. counts must be zeroed by the caller (on the
-// same stream); ext: the snapshot carries the config-5 tables (e, qst: the ElasticQuota gate's status per pod,
-// launch_ext_gate); first_plugin: KG_DIAG_FIRST_PLUGIN. pod_set (nullable; plain snapshots only): the batch carries
-// candidate node sets, tab their record-order table of `words` 64-bit words per set (kg_sets.h).
-hipError_t launch_diagnose(const NodeRec* nodes, const ZoneRec* zones, const ExtDev& e, bool ext, const PodsDev& pods,
-                           const uint32_t* rows, uint32_t n_rows, uint32_t n_nodes, const KCfg& cfg, bool exact,
-                           const uint32_t* qst, bool first_plugin, uint32_t* counts, hipStream_t s,
-                           const int32_t* pod_set = nullptr, const uint64_t* tab = nullptr, uint32_t words = 0);
+// counted status words of f's row t over every record. counts must be zeroed by the caller (on the same stream);
+// first_plugin: KG_DIAG_FIRST_PLUGIN.
+hipError_t launch_diagnose(const RowFilter& f, bool first_plugin, uint32_t* counts, hipStream_t s);
 
 }  // namespace kg

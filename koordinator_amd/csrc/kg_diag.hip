@@ -9,18 +9,14 @@
 //               A byte holds at most 255, so a lane walks at most DIAG_MAX_CHUNK records per launch; the chunk's
 //               nonzero counters are then added into the row's KG_DIAG_SLOTS counters by atomicAdd (integer adds:
 //               exact in any order).
-// The plain plugin set evaluates a pair with eval_pair (filters only: no score, no zone), the config-5 set with
-// eval_pair_ext behind the ElasticQuota gate, as the verify kernels do: the status words are theirs bit for bit.
+// The pair's status word comes from row_status (kg_rowfilter.h): kg_eval_verify's bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 
-#include "kg_cpuset_reserve.h"
 #include "kg_diag.h"
-#include "kg_ext.h"
-#include "kg_ext_wave.h"
-#include "kg_kernels.h"
+#include "kg_rowfilter.h"
 
 namespace kg {
 
@@ -77,55 +73,40 @@ __device__ __forceinline__ void diag_flush(const DiagAcc& a, uint32_t* __restric
 // Records [begin + chunk * y, ...) of [begin, end) for the rows of block x; counts[t][KG_DIAG_SLOTS] zeroed by the
 // launcher. chunk <= DIAG_MAX_CHUNK.
 // SETS (plain plugin set only): the batch carries candidate node sets. The lane keeps its set's 64-bit word of the
-// record-order table for the 64-record block it walks (reloaded when the wave-uniform record index crosses a block;
-// a pod without a set: all ones). A record outside the set adds KG_ST_NODE_EXCLUDED to the counted word or, with
-// first_plugin, is counted under that bit alone: the host's Filter ran before every koord plugin (there is no
-// ElasticQuota gate on the plain path). Without SETS the three arguments are not read.
-template <bool EXACT, bool EXT, bool SETS = false>
+// record-order table for the 64-record block it walks (reloaded when the wave-uniform record index crosses a block).
+// A record outside the set has KG_ST_NODE_EXCLUDED in its word; with first_plugin it is counted under that bit alone
+// (the bit belongs to no plugin group, diag_first_plugin would strip it): the host's Filter ran before every koord
+// plugin (there is no ElasticQuota gate on the plain path). Without SETS the three arguments are not read.
+template <bool EXACT, bool EXT, bool SETS>
 __global__ __launch_bounds__(256) void k_diagnose(const NodeRec* __restrict__ nodes, const ZoneRec* __restrict__ zones,
                                                   ExtDev e, PodsDev pods, const uint32_t* __restrict__ rows,
                                                   uint32_t n_rows, uint32_t begin, uint32_t end, uint32_t chunk, KCfg cfg,
                                                   const uint32_t* __restrict__ qst, uint32_t first_plugin,
                                                   uint32_t* __restrict__ counts, const int32_t* __restrict__ pod_set,
                                                   const uint64_t* __restrict__ tab, uint32_t words) {
-    static_assert(!(EXT && SETS), "candidate node sets are not served on config-5 snapshots");
     const GridBlock b = xcd_block();  // whole record chunks per XCD (kg_eval.h)
     const uint32_t t = b.x * blockDim.x + threadIdx.x;
     if ((t & ~63u) >= n_rows) return;  // uniform: a wave past the last row (no barrier below)
     const bool live = t < n_rows;
     const uint32_t j = live ? (rows ? rows[t] : t) : 0u;
-    const PodV p = load_pod(pods, j);
+    static_assert(!(EXT && SETS), "candidate node sets are not served on config-5 snapshots");
+    const RowCtx c = row_ctx<EXT>(pods, j, live, &e, qst);
+    const RowSet rs = row_set<SETS>(pod_set, tab, words, j);
     const uint32_t lo = begin + b.y * chunk;
     const uint32_t hi = min(end, lo + chunk);
     DiagAcc a;
 #pragma unroll
     for (int s = 0; s < 8; s++) a.w[s] = a.d[s] = 0u;
-    if constexpr (EXT) {
-        const PodX px = load_podx(pods, j);
-        const uint32_t q = live ? qst[j] : 1u;  // idle lanes: decided, no pair evaluated
-        for (uint32_t rec = lo; rec < hi; rec++) {
-            uint32_t w = eval_pair_ext<EXACT>(cfg, e, nodes[rec].v, zones + rec, dev_of(e, rec), rec, p, px, q).status;
-            if (first_plugin) w = diag_first_plugin(w);
-            diag_count(a, w, diag_derived(w));
+    uint64_t cand = ~0ull;
+    for (uint32_t rec = lo; rec < hi; rec++) {
+        if constexpr (SETS)
+            if (rs.set >= 0 && (rec == lo || (rec & 63u) == 0u)) cand = row_cand(rs, rec);
+        uint32_t w = row_status<EXACT, EXT, SETS>(cfg, c, nodes[rec].v, zones + rec, rec, cand);
+        if (first_plugin) {
+            if constexpr (SETS) w = (w & KG_ST_NODE_EXCLUDED) ? (uint32_t)KG_ST_NODE_EXCLUDED : diag_first_plugin(w);
+            else w = diag_first_plugin(w);
         }
-    } else if constexpr (SETS) {
-        const int32_t set = pod_set[j];
-        const uint64_t* srow = tab + (size_t)(set < 0 ? 0 : set) * words;
-        uint64_t word = ~0ull;
-        for (uint32_t rec = lo; rec < hi; rec++) {
-            if (set >= 0 && (rec == lo || (rec & 63u) == 0u)) word = srow[rec >> 6];
-            uint32_t w = eval_pair<EXACT, false, true, false, false>(cfg, nodes[rec].v, zones + rec, p).status;
-            const bool excl = !((word >> (rec & 63u)) & 1ull);
-            if (first_plugin) w = excl ? (uint32_t)KG_ST_NODE_EXCLUDED : diag_first_plugin(w);
-            else w |= excl ? (uint32_t)KG_ST_NODE_EXCLUDED : 0u;
-            diag_count(a, w, diag_derived(w));
-        }
-    } else {
-        for (uint32_t rec = lo; rec < hi; rec++) {
-            uint32_t w = eval_pair<EXACT, false, true, false, false>(cfg, nodes[rec].v, zones + rec, p).status;
-            if (first_plugin) w = diag_first_plugin(w);
-            diag_count(a, w, diag_derived(w));
-        }
+        diag_count(a, w, diag_derived(w));
     }
     if (live) diag_flush(a, counts + (size_t)t * KG_DIAG_SLOTS);
 }
@@ -138,35 +119,22 @@ static uint32_t diag_target_blocks() {
     return (x >= 1 && x <= 65536) ? (uint32_t)x : DIAG_TARGET_BLOCKS;
 }
 
-hipError_t launch_diagnose(const NodeRec* nodes, const ZoneRec* zones, const ExtDev& e, bool ext, const PodsDev& pods,
-                           const uint32_t* rows, uint32_t n_rows, uint32_t n_nodes, const KCfg& cfg, bool exact,
-                           const uint32_t* qst, bool first_plugin, uint32_t* counts, hipStream_t s,
-                           const int32_t* pod_set, const uint64_t* tab, uint32_t words) {
-    if (n_rows == 0 || n_nodes == 0) return hipSuccess;
-    if (pod_set && (ext || !tab || words != (n_nodes + 63) / 64)) return hipErrorInvalidValue;
+hipError_t launch_diagnose(const RowFilter& f, bool first_plugin, uint32_t* counts, hipStream_t s) {
+    if (f.n_rows == 0 || f.n_nodes == 0) return hipSuccess;
+    if (!rowfilter_valid(f) || !counts) return hipErrorInvalidValue;
     // whole waves of rows, up to four per workgroup: a short row list leaves no idle wave walking records
-    const uint32_t block = std::min<uint32_t>(256u, (n_rows + 63u) / 64u * 64u);
-    const uint32_t chunk = diag_chunk(n_nodes, n_rows, block, diag_target_blocks());
-    const uint32_t gx = (n_rows + block - 1) / block;
+    const uint32_t block = std::min<uint32_t>(256u, (f.n_rows + 63u) / 64u * 64u);
+    const uint32_t chunk = diag_chunk(f.n_nodes, f.n_rows, block, diag_target_blocks());
+    const uint32_t gx = (f.n_rows + block - 1) / block;
     constexpr uint32_t MAX_Y = 65535;  // gridDim.y; larger snapshots take several launches
-    for (uint64_t begin = 0; begin < n_nodes; begin += (uint64_t)MAX_Y * chunk) {
-        const uint32_t end = (uint32_t)std::min<uint64_t>(n_nodes, begin + (uint64_t)MAX_Y * chunk);
+    for (uint64_t begin = 0; begin < f.n_nodes; begin += (uint64_t)MAX_Y * chunk) {
+        const uint32_t end = (uint32_t)std::min<uint64_t>(f.n_nodes, begin + (uint64_t)MAX_Y * chunk);
         const dim3 grid(gx, (end - (uint32_t)begin + chunk - 1) / chunk);
-#define KG_DIAG_LAUNCH(EXACT, EXT, ...)                                                                              \
-    k_diagnose<EXACT, EXT, ##__VA_ARGS__><<<grid, block, 0, s>>>(nodes, zones, e, pods, rows, n_rows, (uint32_t)begin, \
-                                                                 end, chunk, cfg, qst, first_plugin ? 1u : 0u, counts, \
-                                                                 pod_set, tab, words)
-        if (pod_set) {
-            if (exact) KG_DIAG_LAUNCH(true, false, true);
-            else KG_DIAG_LAUNCH(false, false, true);
-        } else if (ext) {
-            if (exact) KG_DIAG_LAUNCH(true, true);
-            else KG_DIAG_LAUNCH(false, true);
-        } else {
-            if (exact) KG_DIAG_LAUNCH(true, false);
-            else KG_DIAG_LAUNCH(false, false);
-        }
-#undef KG_DIAG_LAUNCH
+        rowfilter_dispatch(f, [&](auto exact, auto ext, auto sets) {
+            k_diagnose<decltype(exact)::value, decltype(ext)::value, decltype(sets)::value><<<grid, block, 0, s>>>(
+                f.nodes, f.zones, f.e, f.pods, f.rows, f.n_rows, (uint32_t)begin, end, chunk, f.cfg, f.qst,
+                first_plugin ? 1u : 0u, counts, f.pod_set, f.tab, sets_words(f.n_nodes));
+        });
         const hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
     }

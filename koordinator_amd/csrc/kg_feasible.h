@@ -51,20 +51,15 @@ inline uint64_t feasible_span(uint32_t chunk) { return (uint64_t)FEAS_MAX_Y * ch
 #ifndef KG_FEASIBLE_GEOMETRY_ONLY  // the stand-alone host test takes the helpers above only
 #include <hip/hip_runtime_api.h>
 
-#include "kg_kernels.h"
+#include "kg_rowfilter.h"
 
 namespace kg {
 
 // Step 1 (kg_eval_feasible): rtab[t][w], w < feasible_words(n_nodes): bit (r & 63) of word (r >> 6) = the status word
-// of (pod rows[t] (nullptr: pod t), the node stored at record position r) has no bit of fail_mask; bits at or above
-// n_nodes are 0. Every word is written: the caller need not clear rtab. ext: the snapshot carries the config-5 tables
-// (e, qst: the ElasticQuota gate's status per pod, launch_ext_gate). pod_set (nullable; plain snapshots only): the batch
-// carries candidate node sets, tab their record-order table of feasible_words(n_nodes) words per set (kg_sets.h).
-// The form follows feasible_rows_form, or KG_FEASIBLE_FORM=rows|records (read per call).
-hipError_t launch_feasible_records(const NodeRec* nodes, const ZoneRec* zones, const ExtDev& e, bool ext,
-                                   const PodsDev& pods, const uint32_t* rows, uint32_t n_rows, uint32_t n_nodes,
-                                   const KCfg& cfg, bool exact, const uint32_t* qst, uint32_t fail_mask, uint64_t* rtab,
-                                   hipStream_t s, const int32_t* pod_set = nullptr, const uint64_t* tab = nullptr);
+// of (f's row t, the node stored at record position r) has no bit of fail_mask; bits at or above n_nodes are 0. Every
+// word is written: the caller need not clear rtab. The form follows feasible_rows_form, or
+// KG_FEASIBLE_FORM=rows|records (read per call).
+hipError_t launch_feasible_records(const RowFilter& f, uint32_t fail_mask, uint64_t* rtab, hipStream_t s);
 
 // Step 2: out[t][w], w < feasible_words32(n_nodes): bit (i & 31) of word (i >> 5) = rtab[t]'s bit of record position
 // pos[i] (the snapshot index -> record position map); bits at or above n_nodes are 0. count (nullable, zeroed by the

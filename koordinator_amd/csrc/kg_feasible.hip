@@ -13,27 +13,22 @@
 //                            framework's cycle asks for one pod), where lane = row leaves most lanes idle.
 //   step 2  k_feasible_rows  the inverse of k_sets_table: lane = snapshot position i of one row reads the bit of record
 //                            position pos[i]; the ballot's halves are two 32-bit output words.
-// The plain plugin set evaluates a pair with eval_pair (filters only: no score, no zone), the config-5 set with
-// eval_pair_ext behind the ElasticQuota gate, exactly as k_diagnose does with flags 0: the status words are
-// kg_eval_verify's bit for bit. No MFMA: integer / IEEE-double scalar work.
+// The pair's status word comes from row_status (kg_rowfilter.h), as k_diagnose's with flags 0: kg_eval_verify's bit for
+// bit. No MFMA: integer / IEEE-double scalar work.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
-#include "kg_cpuset_reserve.h"
-#include "kg_ext.h"
-#include "kg_ext_wave.h"
 #include "kg_feasible.h"
-#include "kg_kernels.h"
+#include "kg_rowfilter.h"
 
 namespace kg {
 
 // Records [begin + chunk * y, ...) of [begin, end) for the rows of block x. begin and chunk are multiples of 64.
-// SETS (plain plugin set only): the lane keeps its set's word of the record-order table for the 64 records it walks (a
-// pod without a set: all ones); a record outside the set takes KG_ST_NODE_EXCLUDED. Without SETS pod_set and tab are
-// not read; without EXT e and qst are not.
+// SETS (plain plugin set only): the lane keeps its set's word of the record-order table for the 64 records it walks.
+// Without SETS pod_set and tab are not read; without EXT e and qst are not.
 template <bool EXACT, bool EXT, bool SETS>
 __global__ __launch_bounds__(256) void k_feasible_by_rows(const NodeRec* __restrict__ nodes,
                                                           const ZoneRec* __restrict__ zones, ExtDev e, PodsDev pods,
@@ -42,38 +37,23 @@ __global__ __launch_bounds__(256) void k_feasible_by_rows(const NodeRec* __restr
                                                           const uint32_t* __restrict__ qst, uint32_t fail_mask,
                                                           uint64_t* __restrict__ rtab, const int32_t* __restrict__ pod_set,
                                                           const uint64_t* __restrict__ tab, uint32_t words) {
-    static_assert(!(EXT && SETS), "candidate node sets are not served on config-5 snapshots");
     const GridBlock b = xcd_block();  // whole record chunks per XCD (kg_eval.h)
     const uint32_t t = b.x * blockDim.x + threadIdx.x;
     if ((t & ~63u) >= n_rows) return;  // uniform: a wave past the last row (no barrier below)
     const bool live = t < n_rows;
     const uint32_t j = live ? (rows ? rows[t] : t) : 0u;
-    const PodV p = load_pod(pods, j);
+    static_assert(!(EXT && SETS), "candidate node sets are not served on config-5 snapshots");
+    const RowCtx c = row_ctx<EXT>(pods, j, live, &e, qst);
+    const RowSet rs = row_set<SETS>(pod_set, tab, words, j);
     const uint32_t lo = begin + b.y * chunk;
     const uint32_t hi = min(end, lo + chunk);
     uint64_t* __restrict__ dst = rtab + (size_t)(live ? t : 0u) * words;
-    PodX px{};
-    uint32_t q = 0u;
-    if constexpr (EXT) {
-        px = load_podx(pods, j);
-        q = live ? qst[j] : 1u;  // idle lanes: decided, no pair evaluated
-    }
-    int32_t set = -1;
-    if constexpr (SETS) set = pod_set[j];
-    const uint64_t* srow = tab + (size_t)(set < 0 ? 0 : set) * words;
     for (uint32_t w0 = lo; w0 < hi; w0 += 64u) {  // one word of the row: records [w0, w1), w0 a multiple of 64
         const uint32_t w1 = min(hi, w0 + 64u);
-        uint64_t cand = ~0ull;
-        if constexpr (SETS)
-            if (set >= 0) cand = srow[w0 >> 6];
+        const uint64_t cand = row_cand(rs, w0);
         uint64_t acc = 0ull;
         for (uint32_t rec = w0; rec < w1; rec++) {
-            uint32_t st;
-            if constexpr (EXT)
-                st = eval_pair_ext<EXACT>(cfg, e, nodes[rec].v, zones + rec, dev_of(e, rec), rec, p, px, q).status;
-            else
-                st = eval_pair<EXACT, false, true, false, false>(cfg, nodes[rec].v, zones + rec, p).status;
-            if constexpr (SETS) st |= ((cand >> (rec & 63u)) & 1ull) ? 0u : (uint32_t)KG_ST_NODE_EXCLUDED;
+            const uint32_t st = row_status<EXACT, EXT, SETS>(cfg, c, nodes[rec].v, zones + rec, rec, cand);
             acc |= (uint64_t)((st & fail_mask) == 0u) << (rec & 63u);
         }
         if (live) dst[w0 >> 6] = acc;
@@ -89,23 +69,16 @@ __global__ __launch_bounds__(256) void k_feasible_by_records(const NodeRec* __re
                                                              uint32_t fail_mask, uint64_t* __restrict__ rtab,
                                                              const int32_t* __restrict__ pod_set,
                                                              const uint64_t* __restrict__ tab, uint32_t words) {
-    static_assert(!(EXT && SETS), "candidate node sets are not served on config-5 snapshots");
     const uint32_t rec = blockIdx.x * 256u + threadIdx.x;
     const uint32_t t = row_base + blockIdx.y;
     const uint32_t j = rows ? rows[t] : t;  // uniform over the workgroup
     bool ok = false;
     if (rec < n_nodes) {
-        const PodV p = load_pod(pods, j);
-        uint32_t st;
-        if constexpr (EXT)
-            st = eval_pair_ext<EXACT>(cfg, e, nodes[rec].v, zones + rec, dev_of(e, rec), rec, p, load_podx(pods, j), qst[j])
-                     .status;
-        else
-            st = eval_pair<EXACT, false, true, false, false>(cfg, nodes[rec].v, zones + rec, p).status;
-        if constexpr (SETS) {
-            const int32_t set = pod_set[j];
-            if (set >= 0 && !((tab[(size_t)set * words + (rec >> 6)] >> (rec & 63u)) & 1ull)) st |= KG_ST_NODE_EXCLUDED;
-        }
+        static_assert(!(EXT && SETS), "candidate node sets are not served on config-5 snapshots");
+        const RowCtx c = row_ctx<EXT>(pods, j, true, &e, qst);
+        uint32_t st = row_status<EXACT, EXT, false>(cfg, c, nodes[rec].v, zones + rec, rec, ~0ull);
+        // the set and its candidate word (uniform over the wave) are fetched after the evaluation
+        if constexpr (SETS) st = row_exclude(st, row_set<true>(pod_set, tab, words, j), rec);
         ok = (st & fail_mask) == 0u;
     }
     const uint64_t word = __ballot(ok);
@@ -145,26 +118,11 @@ static bool feasible_by_rows(uint32_t n_rows, uint32_t n_nodes) {
     return feasible_rows_form(n_rows, n_nodes);
 }
 
-hipError_t launch_feasible_records(const NodeRec* nodes, const ZoneRec* zones, const ExtDev& e, bool ext,
-                                   const PodsDev& pods, const uint32_t* rows, uint32_t n_rows, uint32_t n_nodes,
-                                   const KCfg& cfg, bool exact, const uint32_t* qst, uint32_t fail_mask, uint64_t* rtab,
-                                   hipStream_t s, const int32_t* pod_set, const uint64_t* tab) {
+hipError_t launch_feasible_records(const RowFilter& f, uint32_t fail_mask, uint64_t* rtab, hipStream_t s) {
+    const uint32_t n_rows = f.n_rows, n_nodes = f.n_nodes;
     if (n_rows == 0 || n_nodes == 0) return hipSuccess;
-    if (!rtab || (pod_set && (ext || !tab)) || (ext && !qst)) return hipErrorInvalidValue;
-    const uint32_t words = feasible_words(n_nodes);
-#define KG_FEAS_DISPATCH(LAUNCH)                           \
-    do {                                                   \
-        if (pod_set) {                                     \
-            if (exact) LAUNCH(true, false, true);          \
-            else LAUNCH(false, false, true);               \
-        } else if (ext) {                                  \
-            if (exact) LAUNCH(true, true, false);          \
-            else LAUNCH(false, true, false);               \
-        } else {                                           \
-            if (exact) LAUNCH(true, false, false);         \
-            else LAUNCH(false, false, false);              \
-        }                                                  \
-    } while (0)
+    if (!rowfilter_valid(f) || !rtab) return hipErrorInvalidValue;
+    const uint32_t words = feasible_words(n_nodes);  // rtab's row and, as sets_words(n_nodes), the table's
     if (feasible_by_rows(n_rows, n_nodes)) {
         // whole waves of rows, up to four per workgroup: a short row list leaves no idle wave walking records
         const uint32_t block = std::min<uint32_t>(256u, (n_rows + 63u) / 64u * 64u);
@@ -173,12 +131,11 @@ hipError_t launch_feasible_records(const NodeRec* nodes, const ZoneRec* zones, c
         for (uint64_t begin = 0; begin < n_nodes; begin += feasible_span(chunk)) {
             const uint32_t end = (uint32_t)std::min<uint64_t>(n_nodes, begin + feasible_span(chunk));
             const dim3 grid(gx, (end - (uint32_t)begin + chunk - 1) / chunk);
-#define KG_FEAS_ROWS(EXACT, EXT, SETS)                                                                                \
-    k_feasible_by_rows<EXACT, EXT, SETS><<<grid, block, 0, s>>>(nodes, zones, e, pods, rows, n_rows, (uint32_t)begin, \
-                                                                end, chunk, cfg, qst, fail_mask, rtab, pod_set, tab,  \
-                                                                words)
-            KG_FEAS_DISPATCH(KG_FEAS_ROWS);
-#undef KG_FEAS_ROWS
+            rowfilter_dispatch(f, [&](auto exact, auto ext, auto sets) {
+                k_feasible_by_rows<decltype(exact)::value, decltype(ext)::value, decltype(sets)::value>
+                    <<<grid, block, 0, s>>>(f.nodes, f.zones, f.e, f.pods, f.rows, n_rows, (uint32_t)begin, end, chunk,
+                                            f.cfg, f.qst, fail_mask, rtab, f.pod_set, f.tab, words);
+            });
             const hipError_t err = hipGetLastError();
             if (err != hipSuccess) return err;
         }
@@ -187,15 +144,14 @@ hipError_t launch_feasible_records(const NodeRec* nodes, const ZoneRec* zones, c
     const uint32_t gx = (n_nodes + 255u) / 256u;
     for (uint32_t base = 0; base < n_rows; base += std::min(n_rows - base, FEAS_MAX_Y)) {
         const dim3 grid(gx, std::min(n_rows - base, FEAS_MAX_Y));
-#define KG_FEAS_RECS(EXACT, EXT, SETS)                                                                               \
-    k_feasible_by_records<EXACT, EXT, SETS><<<grid, 256, 0, s>>>(nodes, zones, e, pods, rows, base, n_nodes, cfg, qst, \
-                                                                 fail_mask, rtab, pod_set, tab, words)
-        KG_FEAS_DISPATCH(KG_FEAS_RECS);
-#undef KG_FEAS_RECS
+        rowfilter_dispatch(f, [&](auto exact, auto ext, auto sets) {
+            k_feasible_by_records<decltype(exact)::value, decltype(ext)::value, decltype(sets)::value>
+                <<<grid, 256, 0, s>>>(f.nodes, f.zones, f.e, f.pods, f.rows, base, n_nodes, f.cfg, f.qst, fail_mask, rtab,
+                                      f.pod_set, f.tab, words);
+        });
         const hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
     }
-#undef KG_FEAS_DISPATCH
     return hipSuccess;
 }
 

@@ -278,20 +278,16 @@ struct kg_pods {
         res_lanes = res_fetched = false;
     }
     DevBuf<uint32_t> d_reason;  // replay: per pod OR of the filter status bits (kg_replay out_reason)
-    // kg_eval_diagnose: the requested rows and their KG_DIAG_SLOTS counters, grown on demand (ensure_diag)
-    DevBuf<uint32_t> d_diag_rows;
-    DevBuf<uint32_t> d_diag;
-    size_t diag_cap = 0;  // rows
-    // kg_eval_feasible: the requested rows, their record-order bitmap (step 1), the snapshot-order output (step 2) and
-    // the per-row population counts, grown on demand (ensure_feasible)
-    DevBuf<uint32_t> d_feas_rows;
+    // The row-list evaluators' scratch, grown on demand: no allocation on the steady path. Each buffer keeps its own
+    // capacity (DevBuf::cap), so a failed grow leaves nothing to reset.
+    DevBuf<uint32_t> d_rows;  // the caller's row list, for the length of one call (stage_rowfilter)
+    DevBuf<uint32_t> d_diag;  // kg_eval_diagnose: the rows' KG_DIAG_SLOTS counters
+    // kg_eval_feasible: the rows' record-order bitmap (step 1), the snapshot-order output (step 2) and the per-row
+    // population counts
     DevBuf<uint64_t> d_feas_rtab;
     DevBuf<uint32_t> d_feas_out;
     DevBuf<uint32_t> d_feas_count;
-    // kg_eval_offer_slots: the requested rows and the [2][n_nodes] counts and status words in snapshot order, grown on
-    // demand (ensure_slots)
-    DevBuf<uint32_t> d_slot_rows;
-    DevBuf<uint32_t> d_slot_out;
+    DevBuf<uint32_t> d_slot_out;  // kg_eval_offer_slots: the [2][n_nodes] counts and status words in snapshot order
     DevBuf<DevSum> d_devsum;    // per record DevSum of the last config-5 select
     DevBuf<uint64_t> d_gz;      // gpu_zone_sum per (class-1 record, GPU request class) of the last config-5 select
     DevBuf<uint8_t> d_rcode;    // [kg_rsv_dev table][DEV_CLASSES]: GPU allocator outcome on the restore tables
@@ -912,23 +908,45 @@ void bracket_drop(kg_ctx* ctx, hipEvent_t a, hipEvent_t b) {
     if (a) ctx->ev_free.emplace_back(a, b);
 }
 
-kg_status record_begin(kg_ctx* ctx, hipEvent_t* a, hipEvent_t* b) {
-    kg_status st = bracket_take(ctx, a, b);
-    if (st != KG_OK || !*a) return st;
-    const hipError_t e = hipEventRecord(*a, ctx->stream);
-    if (e != hipSuccess) {
-        bracket_drop(ctx, *a, *b);
-        *a = *b = nullptr;
-        HIP_TRY(ctx, e);
+// A kernel-time bracket recorded on ctx->stream (kg_profile_read): begin() takes a pair and records its start, commit()
+// records its stop and puts the pair on ev_live. A bracket that leaves its scope uncommitted (an error return between
+// the two, or a failed record) hands its pair back to the pool. With profiling off it holds nothing and does nothing.
+class Bracket {
+public:
+    explicit Bracket(kg_ctx* c) : ctx(c) {}
+    Bracket(const Bracket&) = delete;
+    Bracket& operator=(const Bracket&) = delete;
+    ~Bracket() { bracket_drop(ctx, a, b); }
+    kg_status begin() {
+        const kg_status st = bracket_take(ctx, &a, &b);
+        if (st != KG_OK || !a) return st;
+        HIP_TRY(ctx, hipEventRecord(a, ctx->stream));
+        return KG_OK;
     }
-    return KG_OK;
-}
+    kg_status commit() {
+        if (!a) return KG_OK;
+        HIP_TRY(ctx, hipEventRecord(b, ctx->stream));
+        ctx->ev_live.emplace_back(a, b);
+        a = b = nullptr;
+        return KG_OK;
+    }
 
-kg_status record_end(kg_ctx* ctx, hipEvent_t a, hipEvent_t b) {
-    if (!a) return KG_OK;
-    HIP_TRY(ctx, hipEventRecord(b, ctx->stream));
-    ctx->ev_live.emplace_back(a, b);
-    return KG_OK;
+private:
+    kg_ctx* ctx;
+    hipEvent_t a = nullptr, b = nullptr;
+};
+
+// launch() under a bracket of its own: the device work of `call` that kg_profile_read counts as one step. launch
+// returns its first hipError_t; after a failure nothing is committed.
+template <class Launch>
+kg_status bracketed(kg_ctx* ctx, const char* call, Launch&& launch) {
+    Bracket br(ctx);
+    const kg_status st = br.begin();
+    if (st != KG_OK) return st;
+    const hipError_t le = launch();
+    if (le != hipSuccess)
+        return fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR, "%s: %s", call, hipGetErrorString(le));
+    return br.commit();
 }
 
 }  // namespace
@@ -2161,15 +2179,46 @@ kg_status kg_eval_verify(kg_snap* s, kg_pods* p, kg_verify_out* out) {
     return KG_OK;
 }
 
-// Scratch of kg_eval_diagnose for n_rows requested rows: no allocation on the steady path.
-static kg_status ensure_diag(kg_pods* p, size_t n_rows) {
+// ---- the row-list evaluators: kg_eval_diagnose, kg_eval_feasible, kg_eval_offer_slots -----------------------------
+// Each asks for the Filter status word of (row, node record) pairs over the caller's row list (kg_rowfilter.h) and
+// checks, in this order: the pair, its own arguments, the row list, its outputs, the snapshot side. The three share
+// the steps below; the early-outs (no rows, no nodes) are each call's own.
+
+// rows (NULL: every pod, in batch order) names pods of the batch.
+static kg_status check_rows(kg_pods* p, const uint32_t* rows, uint32_t n_rows) {
     kg_ctx* ctx = p->ctx;
-    if (n_rows <= p->diag_cap) return KG_OK;
-    p->diag_cap = 0;
-    const size_t cap = std::max<size_t>(n_rows, 64);
-    HIP_TRY(ctx, grow(ctx, p->d_diag, KG_DIAG_SLOTS * cap));
-    HIP_TRY(ctx, grow(ctx, p->d_diag_rows, cap));
-    p->diag_cap = cap;
+    if (!rows && n_rows != p->n)
+        return fail(ctx, KG_INVALID_ARG, "rows == NULL with n_rows %u != batch size %u", n_rows, p->n);
+    if (rows)
+        for (uint32_t t = 0; t < n_rows; t++)
+            if (rows[t] >= p->n) return fail(ctx, KG_INVALID_ARG, "rows[%u] = %u >= batch size %u", t, rows[t], p->n);
+    return KG_OK;
+}
+
+// The snapshot side of a row-list call. what: "<the call> on a snapshot with config-5 tables"; ext_served: the call
+// runs on such a snapshot (without candidate node sets), otherwise it is KG_UNSUPPORTED there.
+static kg_status check_rowlist_snap(kg_snap* s, kg_pods* p, const char* what, bool ext_served) {
+    kg_status st = check_views(s);
+    if (st != KG_OK) return st;
+    if (s->ext()) {
+        if (!ext_served) return fail(s->ctx, KG_UNSUPPORTED, "%s", what);
+        st = refuse_sets(s, p, what);
+        if (st != KG_OK) return st;
+        st = check_ext(s);
+        if (st != KG_OK) return st;
+    }
+    return ensure_sets(s, p);
+}
+
+// The launch description of a row-list call, its list uploaded into the batch's staging buffer (64-row floor: no
+// allocation on the steady path). The context mutex serialises the calls and each synchronises before it returns, so
+// the staged list never outlives its call.
+static kg_status stage_rowfilter(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_t n_rows, RowFilter* f) {
+    kg_ctx* ctx = s->ctx;
+    HIP_TRY(ctx, grow(ctx, p->d_rows, std::max<size_t>(n_rows, 64)));
+    if (rows) HIP_TRY(ctx, hipMemcpyAsync(p->d_rows, rows, sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice, ctx->stream));
+    *f = RowFilter{s->d_nodes, s->d_zones, s->n, s->kcfg, force_exact(), s->ext(), s->ext_dev(), p->d_qst, p->dev,
+                   rows ? p->d_rows.get() : nullptr, n_rows, p->any_set ? p->d_pod_set.get() : nullptr, p->d_set_tab};
     return KG_OK;
 }
 
@@ -2180,21 +2229,10 @@ kg_status kg_eval_diagnose(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_
     kg_ctx* ctx = s->ctx;
     std::lock_guard<std::mutex> g(ctx->mu);
     if (flags & ~KG_DIAG_FIRST_PLUGIN) return fail(ctx, KG_INVALID_ARG, "diagnose flags 0x%x", flags);
-    if (!rows && n_rows != p->n)
-        return fail(ctx, KG_INVALID_ARG, "rows == NULL with n_rows %u != batch size %u", n_rows, p->n);
-    if (rows)
-        for (uint32_t t = 0; t < n_rows; t++)
-            if (rows[t] >= p->n) return fail(ctx, KG_INVALID_ARG, "rows[%u] = %u >= batch size %u", t, rows[t], p->n);
-    if (!out_counts) return fail(ctx, KG_INVALID_ARG, "null counts output");
-    st = check_views(s);
+    st = check_rows(p, rows, n_rows);
     if (st != KG_OK) return st;
-    if (s->ext()) {
-        st = refuse_sets(s, p, "diagnosis on a snapshot with config-5 tables");
-        if (st != KG_OK) return st;
-        st = check_ext(s);
-        if (st != KG_OK) return st;
-    }
-    st = ensure_sets(s, p);
+    if (!out_counts) return fail(ctx, KG_INVALID_ARG, "null counts output");
+    st = check_rowlist_snap(s, p, "diagnosis on a snapshot with config-5 tables", true);
     if (st != KG_OK) return st;
     if (n_rows == 0) return KG_OK;
     const size_t words = (size_t)n_rows * KG_DIAG_SLOTS;
@@ -2203,31 +2241,16 @@ kg_status kg_eval_diagnose(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_
         return KG_OK;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = ensure_diag(p, n_rows);
-    if (st != KG_OK) return st;
+    HIP_TRY(ctx, grow(ctx, p->d_diag, KG_DIAG_SLOTS * std::max<size_t>(n_rows, 64)));
     HIP_TRY(ctx, hipMemsetAsync(p->d_diag, 0, sizeof(uint32_t) * words, ctx->stream));
-    if (rows)
-        HIP_TRY(ctx, hipMemcpyAsync(p->d_diag_rows, rows, sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice, ctx->stream));
-    const ExtDev e = s->ext_dev();
-    if (s->ext())  // the ElasticQuota PreFilter of every pod of the batch, as kg_eval_verify runs it
-        HIP_TRY(ctx, launch_ext_gate(p->dev, p->n, e, s->cfg.plugins, p->d_qst, nullptr, ctx->stream));
-    HIP_TRY(ctx, launch_diagnose(s->d_nodes, s->d_zones, e, s->ext(), p->dev, rows ? p->d_diag_rows : nullptr, n_rows, s->n,
-                                 s->kcfg, force_exact(), p->d_qst, (flags & KG_DIAG_FIRST_PLUGIN) != 0, p->d_diag,
-                                 ctx->stream, p->any_set ? p->d_pod_set : nullptr, p->d_set_tab, sets_words(s->n)));
+    RowFilter f;
+    st = stage_rowfilter(s, p, rows, n_rows, &f);
+    if (st != KG_OK) return st;
+    if (f.ext)  // the ElasticQuota PreFilter of every pod of the batch, as kg_eval_verify runs it
+        HIP_TRY(ctx, launch_ext_gate(p->dev, p->n, f.e, s->cfg.plugins, p->d_qst, nullptr, ctx->stream));
+    HIP_TRY(ctx, launch_diagnose(f, (flags & KG_DIAG_FIRST_PLUGIN) != 0, p->d_diag, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_counts, p->d_diag, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return KG_OK;
-}
-
-// Scratch of kg_eval_feasible for n_rows requested rows over n_nodes nodes: no allocation on the steady path. Each
-// buffer keeps its own capacity (DevBuf::cap), so a failed grow leaves nothing to reset.
-static kg_status ensure_feasible(kg_pods* p, size_t n_rows, uint32_t n_nodes) {
-    kg_ctx* ctx = p->ctx;
-    const size_t rows = std::max<size_t>(n_rows, 64);
-    HIP_TRY(ctx, grow(ctx, p->d_feas_rows, rows));
-    HIP_TRY(ctx, grow(ctx, p->d_feas_count, rows));
-    HIP_TRY(ctx, grow(ctx, p->d_feas_rtab, rows * feasible_words(n_nodes)));
-    HIP_TRY(ctx, grow(ctx, p->d_feas_out, rows * feasible_words32(n_nodes)));
     return KG_OK;
 }
 
@@ -2237,21 +2260,10 @@ kg_status kg_eval_feasible(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_
     if (st != KG_OK) return st;
     kg_ctx* ctx = s->ctx;
     std::lock_guard<std::mutex> g(ctx->mu);
-    if (!rows && n_rows != p->n)
-        return fail(ctx, KG_INVALID_ARG, "rows == NULL with n_rows %u != batch size %u", n_rows, p->n);
-    if (rows)
-        for (uint32_t t = 0; t < n_rows; t++)
-            if (rows[t] >= p->n) return fail(ctx, KG_INVALID_ARG, "rows[%u] = %u >= batch size %u", t, rows[t], p->n);
-    if (!out_bits && n_rows) return fail(ctx, KG_INVALID_ARG, "null bitmap output");
-    st = check_views(s);
+    st = check_rows(p, rows, n_rows);
     if (st != KG_OK) return st;
-    if (s->ext()) {
-        st = refuse_sets(s, p, "feasible bitmaps on a snapshot with config-5 tables");
-        if (st != KG_OK) return st;
-        st = check_ext(s);
-        if (st != KG_OK) return st;
-    }
-    st = ensure_sets(s, p);
+    if (!out_bits && n_rows) return fail(ctx, KG_INVALID_ARG, "null bitmap output");
+    st = check_rowlist_snap(s, p, "feasible bitmaps on a snapshot with config-5 tables", true);
     if (st != KG_OK) return st;
     if (n_rows == 0) return KG_OK;
     if (s->n == 0) {  // 0 words per row
@@ -2259,30 +2271,24 @@ kg_status kg_eval_feasible(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_
         return KG_OK;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = ensure_feasible(p, n_rows, s->n);
+    const size_t cap = std::max<size_t>(n_rows, 64);
+    HIP_TRY(ctx, grow(ctx, p->d_feas_count, cap));
+    HIP_TRY(ctx, grow(ctx, p->d_feas_rtab, cap * feasible_words(s->n)));
+    HIP_TRY(ctx, grow(ctx, p->d_feas_out, cap * feasible_words32(s->n)));
+    RowFilter f;
+    st = stage_rowfilter(s, p, rows, n_rows, &f);
     if (st != KG_OK) return st;
-    if (rows)
-        HIP_TRY(ctx, hipMemcpyAsync(p->d_feas_rows, rows, sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice, ctx->stream));
     if (out_count) HIP_TRY(ctx, hipMemsetAsync(p->d_feas_count, 0, sizeof(uint32_t) * n_rows, ctx->stream));
-    const ExtDev e = s->ext_dev();
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    st = record_begin(ctx, &e0, &e1);
-    if (st != KG_OK) return st;
-    hipError_t le = hipSuccess;
-    if (s->ext())  // the ElasticQuota PreFilter of every pod of the batch, as kg_eval_verify runs it
-        le = launch_ext_gate(p->dev, p->n, e, s->cfg.plugins, p->d_qst, nullptr, ctx->stream);
-    if (le == hipSuccess)
-        le = launch_feasible_records(s->d_nodes, s->d_zones, e, s->ext(), p->dev, rows ? p->d_feas_rows : nullptr, n_rows,
-                                     s->n, s->kcfg, force_exact(), p->d_qst, fail_mask, p->d_feas_rtab, ctx->stream,
-                                     p->any_set ? p->d_pod_set : nullptr, p->d_set_tab);
-    if (le == hipSuccess)
-        le = launch_feasible_rows(p->d_feas_rtab, s->d_pos, n_rows, s->n, p->d_feas_out,
-                                  out_count ? p->d_feas_count : nullptr, ctx->stream);
-    if (le != hipSuccess) {
-        bracket_drop(ctx, e0, e1);
-        return fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR, "kg_eval_feasible: %s", hipGetErrorString(le));
-    }
-    st = record_end(ctx, e0, e1);
+    st = bracketed(ctx, "kg_eval_feasible", [&] {
+        hipError_t le = hipSuccess;
+        if (f.ext)  // the ElasticQuota PreFilter of every pod of the batch, as kg_eval_verify runs it
+            le = launch_ext_gate(p->dev, p->n, f.e, s->cfg.plugins, p->d_qst, nullptr, ctx->stream);
+        if (le == hipSuccess) le = launch_feasible_records(f, fail_mask, p->d_feas_rtab, ctx->stream);
+        if (le == hipSuccess)
+            le = launch_feasible_rows(p->d_feas_rtab, s->d_pos, n_rows, s->n, p->d_feas_out,
+                                      out_count ? p->d_feas_count.get() : nullptr, ctx->stream);
+        return le;
+    });
     if (st != KG_OK) return st;
     HIP_TRY(ctx, hipMemcpyAsync(out_bits, p->d_feas_out, sizeof(uint32_t) * (size_t)n_rows * feasible_words32(s->n),
                                 hipMemcpyDeviceToHost, ctx->stream));
@@ -2292,31 +2298,17 @@ kg_status kg_eval_feasible(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_
     return KG_OK;
 }
 
-// Scratch of kg_eval_offer_slots for n_rows requested rows over n_nodes nodes: no allocation on the steady path.
-static kg_status ensure_slots(kg_pods* p, size_t n_rows, uint32_t n_nodes) {
-    kg_ctx* ctx = p->ctx;
-    HIP_TRY(ctx, grow(ctx, p->d_slot_rows, std::max<size_t>(n_rows, 64)));
-    HIP_TRY(ctx, grow(ctx, p->d_slot_out, 2 * std::max<size_t>(n_nodes, 64)));
-    return KG_OK;
-}
-
 kg_status kg_eval_offer_slots(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_t n_rows, uint32_t* out_slots,
                               uint32_t* out_status) {
     kg_status st = check_pair(s, p);
     if (st != KG_OK) return st;
     kg_ctx* ctx = s->ctx;
     std::lock_guard<std::mutex> g(ctx->mu);
-    if (!rows && n_rows != p->n)
-        return fail(ctx, KG_INVALID_ARG, "rows == NULL with n_rows %u != batch size %u", n_rows, p->n);
-    if (rows)
-        for (uint32_t t = 0; t < n_rows; t++)
-            if (rows[t] >= p->n) return fail(ctx, KG_INVALID_ARG, "rows[%u] = %u >= batch size %u", t, rows[t], p->n);
-    if (!out_slots && s->n) return fail(ctx, KG_INVALID_ARG, "null slots output");
-    st = check_views(s);
+    st = check_rows(p, rows, n_rows);
     if (st != KG_OK) return st;
-    if (s->ext())  // Reservation's AddPod moves state its Filter reads (reservation/plugin.go:254-284)
-        return fail(ctx, KG_UNSUPPORTED, "offer slots on a snapshot with config-5 tables");
-    st = ensure_sets(s, p);
+    if (!out_slots && s->n) return fail(ctx, KG_INVALID_ARG, "null slots output");
+    // Reservation's AddPod moves state its Filter reads (reservation/plugin.go:254-284): not on config-5 snapshots
+    st = check_rowlist_snap(s, p, "offer slots on a snapshot with config-5 tables", false);
     if (st != KG_OK) return st;
     if (s->n == 0) return KG_OK;
     if (n_rows == 0) {
@@ -2325,24 +2317,13 @@ kg_status kg_eval_offer_slots(kg_snap* s, kg_pods* p, const uint32_t* rows, uint
         return KG_OK;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = ensure_slots(p, n_rows, s->n);
-    if (st != KG_OK) return st;
-    if (rows)
-        HIP_TRY(ctx, hipMemcpyAsync(p->d_slot_rows, rows, sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice, ctx->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    st = record_begin(ctx, &e0, &e1);
+    HIP_TRY(ctx, grow(ctx, p->d_slot_out, 2 * std::max<size_t>(s->n, 64)));
+    RowFilter f;
+    st = stage_rowfilter(s, p, rows, n_rows, &f);
     if (st != KG_OK) return st;
     uint32_t* d_slots = p->d_slot_out;
     uint32_t* d_status = d_slots + s->n;
-    const hipError_t le = launch_offer_slots(s->d_nodes, s->d_zones, p->dev, rows ? p->d_slot_rows : nullptr, n_rows, s->n,
-                                             s->kcfg, force_exact(), d_slots, d_status, ctx->stream,
-                                             p->any_set ? p->d_pod_set : nullptr, p->d_set_tab, sets_words(s->n));
-    if (le != hipSuccess) {
-        bracket_drop(ctx, e0, e1);
-        return fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR, "kg_eval_offer_slots: %s",
-                    hipGetErrorString(le));
-    }
-    st = record_end(ctx, e0, e1);
+    st = bracketed(ctx, "kg_eval_offer_slots", [&] { return launch_offer_slots(f, d_slots, d_status, ctx->stream); });
     if (st != KG_OK) return st;
     HIP_TRY(ctx, hipMemcpyAsync(out_slots, d_slots, sizeof(uint32_t) * s->n, hipMemcpyDeviceToHost, ctx->stream));
     if (out_status)
@@ -3053,8 +3034,8 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
             return KG_OK;
         }
         // kernel-time bracket (kg_profile_read): the whole config-5 step, DevSum / pass 1 included
-        hipEvent_t e0, e1;
-        st0 = record_begin(ctx, &e0, &e1);
+        Bracket br(ctx);
+        st0 = br.begin();
         if (st0 != KG_OK) return st0;
         // the plain pods' fused select depends on nothing the config-5 kernels build: it runs on the side stream
         // from the fork (after the quota gate has written every pod's status) and joins before the scatters
@@ -3079,7 +3060,7 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         if (st0 != KG_OK) return st0;
         st0 = ext_select_local(s, p, kk, d_out, false, side);
         if (st0 != KG_OK) return st0;
-        return record_end(ctx, e0, e1);
+        return br.commit();
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     {
@@ -3216,8 +3197,8 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         a.fork = ctx->fork;
         a.join = ctx->join;
     }
-    hipEvent_t e0, e1;
-    st = record_begin(ctx, &e0, &e1);
+    Bracket br(ctx);
+    st = br.begin();
     if (st != KG_OK) return st;
     const hipError_t le = a.n_pods ? launch_select(a, ctx->stream) : hipSuccess;
     // a launch error after the fork leaves the pruned lanes' kernels unjoined: drain the side stream before anything
@@ -3241,7 +3222,7 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     }
     // after the side-stream join: every consumer (kg_result_keys, the all-gather, kg_result_status) sees whole tables
     if (dd) HIP_TRY(ctx, launch_expand_keys(p->d_rep, p->n, kk, d_out, p->d_pstat, ctx->stream));
-    return record_end(ctx, e0, e1);
+    return br.commit();
 }
 
 kg_status kg_eval_select(kg_snap* s, kg_pods* p, uint32_t k) {
@@ -3626,8 +3607,8 @@ kg_status kg_replay(kg_snap* s, kg_pods* p, int32_t* out_node, int64_t* out_tota
     if (reasons) HIP_TRY(ctx, hipMemsetAsync(p->d_reason, 0, sizeof(uint32_t) * (n + 1), ctx->stream));
     s->gen++;
     HIP_TRY(ctx, hipMemsetAsync(p->d_step, 0, sizeof(uint32_t), ctx->stream));
-    hipEvent_t e0, e1;
-    st = record_begin(ctx, &e0, &e1);
+    Bracket br(ctx);
+    st = br.begin();
     if (st != KG_OK) return st;
     if (windows) {
         // every window places 1..RB_W pods: launch the windows the remaining pods need at least, then look
@@ -3649,7 +3630,7 @@ kg_status kg_replay(kg_snap* s, kg_pods* p, int32_t* out_node, int64_t* out_tota
         for (uint32_t done = 0; done <= n; done += REPLAY_G) HIP_TRY(ctx, hipGraphLaunch(p->rexec, ctx->stream));
     }
     HIP_TRY(ctx, launch_big_scan(s->d_nodes, s->n, s->d_big + 1, s->d_big, ctx->stream));
-    st = record_end(ctx, e0, e1);
+    st = br.commit();
     if (st != KG_OK) return st;
     std::vector<uint64_t> w(std::max<uint32_t>(n, 1));
     HIP_TRY(ctx, hipMemcpyAsync(w.data(), p->d_winners, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -3776,8 +3757,8 @@ static kg_status ext_replay(kg_snap* s, kg_pods* p, int32_t* out_node, int64_t* 
     s->gen++;
     HIP_TRY(ctx, hipMemsetAsync(p->d_buckets, 0, sizeof(uint64_t) * REPLAY_BUCKET_WORDS, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(p->d_step, 0, sizeof(uint32_t), ctx->stream));
-    hipEvent_t e0, e1;
-    st = record_begin(ctx, &e0, &e1);
+    Bracket br(ctx);
+    st = br.begin();
     if (st != KG_OK) return st;
     // the tables of the replay's starting state (inside the timed region)
     if (replay_dsum(s, p))
@@ -3788,7 +3769,7 @@ static kg_status ext_replay(kg_snap* s, kg_pods* p, int32_t* out_node, int64_t* 
                                          s->ext_dev(), p->d_gz, ctx->stream));
     for (uint32_t done = 0; done <= n; done += REPLAY_G) HIP_TRY(ctx, hipGraphLaunch(p->xexec, ctx->stream));
     HIP_TRY(ctx, launch_big_scan(s->d_nodes, s->n, s->d_big + 1, s->d_big, ctx->stream));
-    st = record_end(ctx, e0, e1);
+    st = br.commit();
     if (st != KG_OK) return st;
     if ((s->cfg.plugins & KG_PLUGIN_RSV) && s->n_views) s->views_on_device = true;  // Reservation.Reserve ran there
     if ((s->cfg.plugins & KG_PLUGIN_QUOTA) && s->n_quotas) {
@@ -4188,14 +4169,14 @@ kg_status kg_batch_schedule(kg_snap* s, kg_pods* p, const int32_t* plan_node, ui
     HIP_TRY(ctx, hipMemcpyAsync(d, h.data(), sizeof(uint32_t) * h.size(), hipMemcpyHostToDevice, ctx->stream));
     st = save_state(s, s->bk);  // CleanupAssumedPods restores this
     if (st != KG_OK) return st;
-    hipEvent_t e0, e1;
-    st = record_begin(ctx, &e0, &e1);
+    Bracket br(ctx);
+    st = br.begin();
     if (st != KG_OK) return st;
     const bool cs = cpuset_active(s, p);  // cpuset-binding pods: the cooperative cycle takes their CPUs on the device
     HIP_TRY(ctx, launch_batch(s->d_nodes, s->d_zones, s->d_dev, s->ext_dev(), p->dev, d, d + G + 1, d + G + 1 + n, G, s->ext(),
                               s->kcfg, force_exact(), d_res, d_res + n, (int32_t*)(d_res + 2 * n), d_res + 3 * n, ctx->stream,
                               cs ? s->d_cpu_alloc : nullptr, cs ? s->d_cpu_topos : nullptr));
-    st = record_end(ctx, e0, e1);
+    st = br.commit();
     if (st != KG_OK) return st;
     std::vector<uint32_t> out(4 * (size_t)n);
     HIP_TRY(ctx, hipMemcpyAsync(out.data(), d_res, sizeof(uint32_t) * 4 * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -4749,8 +4730,8 @@ kg_status kg_shard_select(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* out_keys
         if (st != KG_OK) return st;
         p->result_rows(k, kk);
         if (n == 0) return KG_OK;
-        hipEvent_t e0, e1;  // bracket: the whole shard step (its all-reduces included)
-        st = record_begin(ctx, &e0, &e1);
+        Bracket br(ctx);  // the whole shard step (its all-reduces included)
+        st = br.begin();
         if (st != KG_OK) return st;
         st = ext_stats_local(s, p);
         if (st != KG_OK) return st;
@@ -4768,7 +4749,7 @@ kg_status kg_shard_select(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* out_keys
         } else
             st = ext_select_local(s, p, kk, local, true);
         if (st != KG_OK) return st;
-        st = record_end(ctx, e0, e1);
+        st = br.commit();
     } else {
         st = select_local(s, p, k, local);
     }

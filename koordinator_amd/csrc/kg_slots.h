@@ -4,7 +4,7 @@
 
 #include <cstdint>
 
-#include "kg_kernels.h"
+#include "kg_rowfilter.h"
 
 namespace kg {
 
@@ -20,13 +20,9 @@ constexpr uint32_t SLOTS_WG = 64;
 constexpr uint32_t SLOTS_STAGE = N_FLAGS + 1;
 static_assert(SLOTS_STAGE % 2 == 1, "an odd lane stride in 64-bit words keeps the lanes' LDS reads off one bank");
 
-// Node offer slots (kg_eval_offer_slots): slots[i], status[i] of the node at snapshot position i for the pods
-// rows[0..n_rows) (nullptr: pods 0..n_rows) added one after another, network_topology_solver.go:113-158. Every entry
-// of both outputs is written: the caller need not clear them. Plain snapshots only (no config-5 tables). pod_set
-// (nullable): the batch carries candidate node sets, tab their record-order table of `words` words per set (kg_sets.h).
-hipError_t launch_offer_slots(const NodeRec* nodes, const ZoneRec* zones, const PodsDev& pods, const uint32_t* rows,
-                              uint32_t n_rows, uint32_t n_nodes, const KCfg& cfg, bool exact, uint32_t* slots,
-                              uint32_t* status, hipStream_t s, const int32_t* pod_set = nullptr,
-                              const uint64_t* tab = nullptr, uint32_t words = 0);
+// Node offer slots (kg_eval_offer_slots): slots[i], status[i] of the node at snapshot position i for f's rows added
+// one after another, network_topology_solver.go:113-158. Every entry of both outputs is written: the caller need not
+// clear them. Plain snapshots only (f.ext is refused).
+hipError_t launch_offer_slots(const RowFilter& f, uint32_t* slots, uint32_t* status, hipStream_t s);
 
 }  // namespace kg

@@ -6,7 +6,8 @@
 // is wave-uniform (the pod lives in SGPRs, loaded with scalar loads), k_feasible_by_records' geometry with the pod loop
 // inside. What "add" changes is what NodeInfo.AddPodInfo moves (requested cpu / memory / ephemeral-storage / scalars,
 // non-zero requested cpu / memory, the pod count): exactly the slots struct Over overrides (kg_eval.h). Each lane keeps
-// an Over in registers, seeded from its record, and evaluates eval_pair<OV = true> against it: the LoadAware bases,
+// an Over in registers, seeded from its record, and takes the pair's word against it (row_status with OV,
+// kg_rowfilter.h: the filters-only pair evaluation every row-list call shares): the LoadAware bases,
 // NUMA zone usage, cpusets stay the snapshot's, as the plugins' AddPod hooks leave them for a pending sibling.
 // A lane that failed keeps its word; the wave leaves the loop when no lane is alive. Results go to the node's
 // snapshot position: no atomics, no second pass. No MFMA: integer / IEEE-double scalar work.
@@ -14,13 +15,13 @@
 // iteration, kg_slots.h); the ZoneRec, which only NUMA nodes read, stays in global memory.
 #include <hip/hip_runtime.h>
 
-#include "kg_eval.h"
+#include "kg_rowfilter.h"
 #include "kg_slots.h"
 
 namespace kg {
 
 // grid ceil(n_nodes / SLOTS_WG) workgroups of one wave. SETS: the pod's set word of the record-order table for the
-// wave's 64 records (rec >> 6 is wave-uniform); a record outside the set takes KG_ST_NODE_EXCLUDED beside its word.
+// wave's 64 records (rec >> 6 is wave-uniform).
 template <bool EXACT, bool SETS>
 __global__ __launch_bounds__(SLOTS_WG) void k_offer_slots(const NodeRec* __restrict__ nodes,
                                                           const ZoneRec* __restrict__ zones, PodsDev pods,
@@ -54,15 +55,11 @@ __global__ __launch_bounds__(SLOTS_WG) void k_offer_slots(const NodeRec* __restr
     for (uint32_t t = 0; t < n_rows; t++) {
         if (!__any(alive)) break;  // uniform
         const uint32_t j = __builtin_amdgcn_readfirstlane(rows ? rows[t] : t);
-        const PodV p = load_pod(pods, j);
-        uint64_t cand = ~0ull;
-        if constexpr (SETS) {
-            const int32_t set = pod_set[j];
-            if (set >= 0) cand = tab[(size_t)set * words + (r >> 6)];
-        }
+        const RowCtx c = row_ctx<false>(pods, j, true, nullptr, nullptr);
+        const PodV& p = c.p;
+        const uint64_t cand = row_cand(row_set<SETS>(pod_set, tab, words, j), r);
         if (alive) {
-            uint32_t st = eval_pair<EXACT, true, true, false, false>(cfg, n, zr, p, &ov).status;
-            if constexpr (SETS) st |= ((cand >> (r & 63u)) & 1ull) ? 0u : (uint32_t)KG_ST_NODE_EXCLUDED;
+            const uint32_t st = row_status<EXACT, false, SETS, true>(cfg, c, n, zr, r, cand, &ov);
             if (st) {
                 word = st;
                 alive = false;
@@ -86,25 +83,15 @@ __global__ __launch_bounds__(SLOTS_WG) void k_offer_slots(const NodeRec* __restr
     }
 }
 
-hipError_t launch_offer_slots(const NodeRec* nodes, const ZoneRec* zones, const PodsDev& pods, const uint32_t* rows,
-                              uint32_t n_rows, uint32_t n_nodes, const KCfg& cfg, bool exact, uint32_t* slots,
-                              uint32_t* status, hipStream_t s, const int32_t* pod_set, const uint64_t* tab,
-                              uint32_t words) {
-    if (n_nodes == 0) return hipSuccess;
-    if (!nodes || !zones || !slots || !status || (pod_set && (!tab || words != (n_nodes + 63u) / 64u)))
-        return hipErrorInvalidValue;
-    const uint32_t grid = (n_nodes + SLOTS_WG - 1u) / SLOTS_WG;
-#define KG_SLOTS(EXACT, SETS)                                                                                        \
-    k_offer_slots<EXACT, SETS><<<grid, SLOTS_WG, 0, s>>>(nodes, zones, pods, rows, n_rows, n_nodes, cfg, slots, status, \
-                                                         pod_set, tab, words)
-    if (pod_set) {
-        if (exact) KG_SLOTS(true, true);
-        else KG_SLOTS(false, true);
-    } else {
-        if (exact) KG_SLOTS(true, false);
-        else KG_SLOTS(false, false);
-    }
-#undef KG_SLOTS
+hipError_t launch_offer_slots(const RowFilter& f, uint32_t* slots, uint32_t* status, hipStream_t s) {
+    if (f.n_nodes == 0) return hipSuccess;
+    if (!rowfilter_valid(f) || f.ext || !slots || !status) return hipErrorInvalidValue;
+    const uint32_t grid = (f.n_nodes + SLOTS_WG - 1u) / SLOTS_WG;
+    rowfilter_dispatch<false>(f, [&](auto exact, auto, auto sets) {
+        k_offer_slots<decltype(exact)::value, decltype(sets)::value><<<grid, SLOTS_WG, 0, s>>>(
+            f.nodes, f.zones, f.pods, f.rows, f.n_rows, f.n_nodes, f.cfg, slots, status, f.pod_set, f.tab,
+            sets_words(f.n_nodes));
+    });
     return hipGetLastError();
 }
 

@@ -441,18 +441,22 @@ def eval_verify(snap: Snapshot, pods: PodBatch) -> abi.VerifyResult:
     return res
 
 
+def _row_list(pods: PodBatch, rows):
+    """(n_rows, pointer) of a row-list call's `rows`: None = every pod of the batch (a null pointer)."""
+    if rows is None:
+        return pods.n, None
+    rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
+    # an empty list is not "every pod": it keeps a pointer (data_as holds the array)
+    return len(rows), (rows if len(rows) else np.zeros(1, np.uint32)).ctypes.data_as(C.POINTER(C.c_uint32))
+
+
 def eval_diagnose(snap: Snapshot, pods: PodBatch, rows=None, first_plugin: bool = True) -> np.ndarray:
     """kg_eval_diagnose: reason node counts [n_rows, KG_DIAG_SLOTS] (uint32) of the pods `rows` (batch indices, any
     order, repeats allowed; None = every pod). first_plugin: count each node under its first failing plugin only, as
     the framework's Diagnosis does (reasons.fit_error reads such rows); False: every failing plugin's bits."""
     P = C.POINTER(C.c_uint32)
     flags = abi.KG_DIAG_FIRST_PLUGIN if first_plugin else 0
-    if rows is None:
-        n_rows, rp = pods.n, None
-    else:
-        rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
-        n_rows = len(rows)
-        rp = (rows if n_rows else np.zeros(1, np.uint32)).ctypes.data_as(P)  # an empty list is not "every pod"
+    n_rows, rp = _row_list(pods, rows)
     out = np.zeros((max(n_rows, 1), abi.KG_DIAG_SLOTS), np.uint32)
     snap.ctx.check(snap.ctx.L.kg_eval_diagnose(snap.h, pods.h, rp, n_rows, flags, out.ctypes.data_as(P)),
                    "kg_eval_diagnose")
@@ -465,12 +469,7 @@ def eval_feasible(snap: Snapshot, pods: PodBatch, rows=None, fail_mask: int = 0x
     allowed; None = every pod). The format is set_node_sets' bitmap; nodesets.to_mask turns it into bool[n_rows,
     n_nodes]. counts: also return uint32[n_rows], the rows' population counts."""
     P = C.POINTER(C.c_uint32)
-    if rows is None:
-        n_rows, rp = pods.n, None
-    else:
-        rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
-        n_rows = len(rows)
-        rp = (rows if n_rows else np.zeros(1, np.uint32)).ctypes.data_as(P)  # an empty list is not "every pod"
+    n_rows, rp = _row_list(pods, rows)
     words = (snap.n + 31) // 32
     out = np.zeros((n_rows, words), np.uint32)
     cnt = np.zeros(max(n_rows, 1), np.uint32)
@@ -486,12 +485,7 @@ def eval_offer_slots(snap: Snapshot, pods: PodBatch, rows=None, status: bool = F
     (calculateNodeOfferSlot). status: also return uint32[n_nodes], 0 where every pod passed, else the status word of
     the first pod that did not, on the node with the pods before it added."""
     P = C.POINTER(C.c_uint32)
-    if rows is None:
-        n_rows, rp = pods.n, None
-    else:
-        rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
-        n_rows = len(rows)
-        rp = (rows if n_rows else np.zeros(1, np.uint32)).ctypes.data_as(P)  # an empty list is not "every pod"
+    n_rows, rp = _row_list(pods, rows)
     slots = np.zeros(max(snap.n, 1), np.uint32)
     word = np.zeros(max(snap.n, 1), np.uint32)
     snap.ctx.check(snap.ctx.L.kg_eval_offer_slots(snap.h, pods.h, rp, n_rows, slots.ctypes.data_as(P),

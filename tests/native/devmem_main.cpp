@@ -144,7 +144,7 @@ void test_six() {
     CHECK(live == 0);
 }
 
-// d_diag + d_diag_rows: one logical capacity, set once both buffers stand
+// d_ipairs + d_ipair_count: one logical capacity, set once both buffers stand
 struct Group {
     DevBuf<uint32_t> x, y;
     size_t cap = 0;

@@ -1,6 +1,7 @@
 """Buffers of the host runtime that grow on demand (kg_devmem.h, `grow` in kg_runtime.cpp), each taken through one
 regrow on one context and one PodBatch object, the results before and after it against the CPU oracle:
-kg_eval_diagnose's scratch (64-row floor -> 200 rows), the select's partial rows (300 -> 5,000 nodes and back), the
+kg_eval_diagnose's scratch (64-row floor -> 200 rows), the row list that kg_eval_diagnose, kg_eval_feasible and
+kg_eval_offer_slots stage in one buffer (10 -> 200 -> 33 -> 10 rows, call after call), the select's partial rows (300 -> 5,000 nodes and back), the
 candidate node-set tables (2 -> 40 sets) and the row-update staging (256-row floor -> 400 rows).
 
 Bar: bit-exact (np.array_equal): counts, keys, status words and node state are integers."""
@@ -10,9 +11,11 @@ import numpy as np
 import pytest
 
 import node_sets_ref as ref
+import offer_slots_ref
 import oracle_lib
 from koordinator_amd import abi, engine, nodesets, synth
 from test_diagnose import assert_counts, expected
+from test_feasible import expected as feasible_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -49,6 +52,34 @@ def test_diagnose_regrow(ctx, batch):
     assert_counts(engine.eval_diagnose(snap, batch, rows=many), want[many], "200 rows")
     assert_counts(engine.eval_diagnose(snap, batch, rows=few), want[few], "10 rows again")
     assert want[:200].any() and not np.array_equal(want[few], want[many[:10]])
+
+
+def test_row_list_is_each_calls_own(ctx, batch):
+    """kg_eval_diagnose, kg_eval_feasible and kg_eval_offer_slots stage their row lists in one buffer of the batch:
+    each call uploads its own list, so no call may see the list of the call before it. Every list here gives another
+    result than the list a stale buffer would hold in its place (asserted on the oracle's side below)."""
+    kc, nodes, pods = cluster(300, 256, 21)
+    status = oracle_lib.eval_verify(kc, nodes, pods).status
+    counts, bits = expected(status, True), feasible_bits(status, 0xFFFFFFFF)
+    snap = engine.Snapshot(ctx, kc, nodes)
+    batch.upload(pods)
+    few = np.arange(250, 240, -1, dtype=np.uint32)  # 10 rows: the 64-row floor
+    many = np.arange(200, dtype=np.uint32)[::-1].copy()  # 200 rows: the shared list regrows
+    gang = np.concatenate([np.arange(60, 82), np.arange(60, 71)]).astype(np.uint32)  # 33 rows, 11 of them twice
+    slots = {name: offer_slots_ref.offer_slots(kc, nodes, pods, rows)
+             for name, rows in (("gang", gang), ("gang[:10]", gang[:10]), ("many[:33]", many[:33]))}
+    # a call that kept the list before it would be seen: the lists' results differ
+    assert not np.array_equal(counts[few], counts[many[:10]]) and not np.array_equal(bits[few], bits[many[:10]])
+    assert not np.array_equal(counts[few], counts[gang[:10]])
+    for stale in ("gang[:10]", "many[:33]"):
+        assert not np.array_equal(slots["gang"][0], slots[stale][0]), stale
+        assert not np.array_equal(slots["gang"][1], slots[stale][1]), stale
+    assert_counts(engine.eval_diagnose(snap, batch, rows=few), counts[few], "10 rows")
+    assert np.array_equal(engine.eval_feasible(snap, batch, rows=many), bits[many])
+    got = engine.eval_offer_slots(snap, batch, rows=gang, status=True)
+    assert np.array_equal(got[0], slots["gang"][0]) and np.array_equal(got[1], slots["gang"][1])
+    assert_counts(engine.eval_diagnose(snap, batch, rows=few), counts[few], "10 rows again")
+    assert np.array_equal(engine.eval_feasible(snap, batch, rows=few), bits[few])
 
 
 def test_partial_rows_regrow(ctx, batch, monkeypatch):
