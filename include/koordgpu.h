@@ -689,7 +689,9 @@ kg_status kg_eval_verify(kg_snap* snap, kg_pods* pods, kg_verify_out* out);
 /* Filter + Score + selectHost for every pending pod against the snapshot as it is (matrix mode):
  * per pod the k best packed keys (kg_make_key), descending, 0 = no feasible node. The launch is
  * asynchronous; results stay on the device until kg_result_keys. Where the device kept one result per distinct pod row
- * (the one-launch top-1 select), kg_result_keys and kg_result_status copy those and fill in the rows on the host, through
+ * (the one-launch top-1 select: by default the launch's own accumulators are that result, a few replicas of key and status
+ * words per row, which the readers fold; or one key and status word per row stored by the launch's last workgroup),
+ * kg_result_keys and kg_result_status copy those and fill in the rows on the host, through
  * the row table of the upload that the select ran on; both may be called any number of times, in either order.
  * Read a result before the batch's next kg_pods_upload: the upload replaces that table, and until the next select on
  * the batch both calls then fail with KG_INVALID_ARG ("no selection result") rather than serve rows of the old batch
@@ -897,8 +899,9 @@ kg_status kg_batch_schedule(kg_snap* snap, kg_pods* pods, const int32_t* plan_no
 /* Device time of the select / replay steps: one bracket per step, summed. A step of several device operations is
  * bracketed by HIP events on the launch stream. The one-launch top-1 select of one pod block times
  * itself with the device's wall clock instead (hipDeviceAttributeWallClockRate): its bracket runs from the first
- * workgroup's entry to the completion of the last row store, which leaves out the dispatch's launch ramp and
- * end-of-kernel release (a few microseconds). kg_profile_read waits for the brackets still outstanding. */
+ * workgroup's entry to the completion of the last result write, which leaves out the dispatch's launch ramp and
+ * end-of-kernel release (a few microseconds). Each such launch fills a slot of a device table; kg_profile_read waits for
+ * the brackets still outstanding and returns KG_DEVICE_ERROR when a launch left its slot incomplete. */
 kg_status kg_profile_enable(kg_ctx* ctx, int enable);
 kg_status kg_profile_read(kg_ctx* ctx, double* total_ms, uint64_t* launches, int reset);
 

@@ -73,19 +73,26 @@ struct LaunchSelect {
     // whole waves), the finisher stores each lane's key and status word once and no row; lane_of and n_rows are not
     // read. The reader expands the rows through its own copy of the row -> lane table
     bool small_lanes;
+    // the accumulators are the result (one launch only, never together with small_lanes): skeys / sfhi / sub are one
+    // parity of the batch's result accumulators, [small_replicas][lanes rounded up to whole waves] each and contiguous
+    // in that order; no finisher runs and nothing goes back to zero. Instead the launch zeroes acc_zero_n 16-byte words
+    // at acc_zero: what the previous launch left in the other parity. out, pstat, lane_of and n_rows are not read,
+    // sticket only by a phases launch. The reader folds the replicas and applies the status rule
+    bool small_acc;
+    void* acc_zero;  // 16-byte aligned
+    uint32_t acc_zero_n;
     // optional timing pair of the small select (both set, or neither): the launch binds ev_start to k_select_small's
     // begin and ev_stop to the end of the kernel that finishes the step (hipExtLaunchKernelGGL), instead of the caller
     // recording events around it. Bound only when launch_select returns hipSuccess
     hipEvent_t ev_start, ev_stop;
-    // or (one launch only, never together with the pair) the kernel times itself with the device clock: prof[0] += ticks
-    // from the first workgroup's entry to the finisher's last row store, prof[1] += 1. The begin word of the launch is
-    // the 64-bit word SMALL_BEGIN_WORD of sticket's 128-byte line: zero before and after every launch
+    // or (one launch only, never together with the pair) the kernel times itself with the device clock. prof is a slot
+    // of the launch's own, zero before it: prof[0] = maximum over the workgroups of ~(entry time), prof[1] = maximum of
+    // the end times (the finisher's last result store; small_acc: every slice-0 wave's last result atomic)
     uint64_t* prof;
     // measurement aid (KG_SMALL_PHASES): prof is a scratch pair of the launch's own, followed by [chunks][4] clock
     // readings per workgroup, see k_select_small
     bool phases;
 };
-constexpr uint32_t SMALL_BEGIN_WORD = 8;  // in 64-bit words from sticket
 constexpr uint32_t SMALL_MAX_CHUNK = 64, SMALL_MAX_CHUNKS = 4096;
 constexpr uint32_t SMALL_WG = 1024;  // most threads of a k_select_small workgroup
 inline uint32_t select_fparts(const LaunchSelect& a) { return a.big_part0 + a.big_y; }

@@ -286,22 +286,27 @@ __global__ __launch_bounds__(256) KG_SEL1_ATTR void k_select1(const NodeRec* __r
 // inline integer path fits without scratch) or 1024 (128 VGPRs: it spills; more copies per workgroup). The chunks are
 // dealt to the XCDs in contiguous runs (xcd_block; launch order measured the same).
 // prof (nullable; only with acc_r > 0): the launch times itself for kg_profile_read with the device-wide 100 MHz clock
-// (wall_clock64), so that the dispatch carries no event pair. Thread 0 of every workgroup folds the complement of its
-// entry time into the begin word (SMALL_BEGIN_WORD: on the ticket's line, zero between launches like every word of
-// that buffer; the maximum of the complements is the complement of the earliest entry), long before the drain and the ticket that
-// publish the accumulators, so they publish it too. The finisher takes the word back to zero with its other exchanges
-// and, once its result stores (rows or lanes) have completed, adds end - begin to prof[0] and 1 to prof[1]. With prof == nullptr the
-// kernel runs two uniform branches more and nothing else.
+// (wall_clock64), so that the dispatch carries no event pair. prof is the launch's own slot of the context's table,
+// zero when the launch starts: {maximum of the complements of the entry times, maximum of the end times}. Thread 0 of
+// every workgroup folds the complement of its entry time into prof[0] (the maximum of the complements is the complement
+// of the earliest entry). The end: the finisher, once its result stores (rows or lanes) have completed; without a
+// finisher (SMALL_FORM_ACC) every slice-0 wave, once its own result atomics have completed. The host reads and
+// re-zeroes the slot. With prof == nullptr the kernel runs two uniform branches more and nothing else.
 // PH (KG_SMALL_PHASES, a measurement aid; off in every instantiation the library launches by default): prof is set and
 // the launch's own scratch pair, followed by four clock readings per workgroup that thread 0 stores: entry, loops done
-// (after the slices met in LDS), ticket drawn and, the finisher only (else zero), results stored.
+// (after the slices met in LDS), ticket drawn (SMALL_FORM_ACC: result atomics complete) and, the finisher only
+// (SMALL_FORM_ACC: the workgroup that draws PH's last ticket; else zero), results stored.
 // form (uniform; acc_r > 0 only): what the finisher stores. SMALL_FORM_ROWS / SMALL_FORM_ROWS4: out / pstat of every
 // row through lane_of, one by one or four at a time (below). SMALL_FORM_LANES: out and pstat are per-lane tables of lp
 // entries and slice 0's thread j < n_lanes stores its lane's key and status word to out[j] / pstat[j]; lane_of and
 // n_rows are not read, the launch's cost does not depend on the row count, and whoever reads the result expands it
 // (kg_result_keys on the host, through the same row -> lane table). One workgroup alone on the chip storing
-// n_rows x 12 bytes was 2 of the finisher's 3.3 us at config 2's 10,000 rows.
-constexpr uint32_t SMALL_FORM_ROWS = 0, SMALL_FORM_ROWS4 = 1, SMALL_FORM_LANES = 2;
+// n_rows x 12 bytes was 2 of the finisher's 3.3 us at config 2's 10,000 rows. SMALL_FORM_ACC: no
+// finisher at all; skeys / sfhi / sub are one parity of the batch's result accumulators and stay as the launch leaves
+// them, the reader folds the replicas and applies the status rule (fold_acc, kg_runtime.cpp); zero / zero_n are the
+// other parity's dirty 16-byte words (0 in every other form), out, pstat, lane_of and n_rows are not read, and ticket
+// only by PH.
+constexpr uint32_t SMALL_FORM_ROWS = 0, SMALL_FORM_ROWS4 = 1, SMALL_FORM_LANES = 2, SMALL_FORM_ACC = 3;
 constexpr uint32_t SMALL_ROW_STEPS = 4;  // the finisher's lane words in flight per thread
 template <uint32_t PM, uint32_t WG, bool PH = false>
 __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__ nodes, const ZoneRec* __restrict__ zones,
@@ -313,18 +318,29 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
                                                            uint32_t* __restrict__ ticket,
                                                            const uint8_t* __restrict__ lane_of, uint32_t n_rows,
                                                            uint64_t* __restrict__ out, uint32_t* __restrict__ pstat,
-                                                           uint64_t* __restrict__ prof, uint32_t form) {
+                                                           uint64_t* __restrict__ prof, uint32_t form,
+                                                           uint4* __restrict__ zero, uint32_t zero_n) {
     __shared__ uint64_t lk[WG];
     __shared__ uint2 ls[WG];
+    __shared__ uint32_t acc_done;  // prof in SMALL_FORM_ACC: slice-0 waves whose result atomics have completed
     uint64_t ph_entry = 0, ph_loops = 0;
-    uint64_t* const pbegin = reinterpret_cast<uint64_t*>(ticket) + SMALL_BEGIN_WORD;
     uint64_t* const phases = prof + 2;  // PH only
     if (PH || prof) {  // uniform
         const uint64_t t_in = wall_clock64();
         if (PH) ph_entry = t_in;
-        if (prof && threadIdx.x == 0) __hip_atomic_fetch_max(pbegin, ~t_in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (prof && threadIdx.x == 0) {
+            acc_done = 0u;
+            __hip_atomic_fetch_max(prof, ~t_in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
     const uint32_t c = xcd_block().y, slices = blockDim.x / lp;
+    // SMALL_FORM_ACC: what the previous launch on the batch left in the other parity's accumulators goes back to zero.
+    // Whole 128-byte lines: line c + k * chunks to workgroup c, eight neighbouring lanes a 16-byte word each, so that
+    // no line is written from two workgroups (two XCDs' L2s); nothing waits on the stores
+    for (uint32_t i = (c + (threadIdx.x >> 3) * gridDim.y) * 8u + (threadIdx.x & 7u); i < zero_n;
+         i += (blockDim.x >> 3) * gridDim.y * 8u) {
+        zero[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
     const uint32_t j = threadIdx.x % lp;
     const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / lp));  // lp is whole waves
     const bool live = j < n_lanes;
@@ -409,6 +425,45 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
         sub[slot] = live ? st.y : 0u;
         return;
     }
+    // SMALL_FORM_ACC: the accumulators are the result. Slice 0 folds into replica c % acc_r as the finisher forms do
+    // (below), into the parity that the launch before zeroed, and the workgroup is done: no ticket, no barrier, no
+    // acquire, nothing read back. The other slices' waves have left after the LDS barrier. With prof every slice-0 wave
+    // waits for its own atomics and counts itself in LDS (acc_done, no wave waits for another); the wave that counts
+    // last reads the clock, behind the completion of every result atomic of the workgroup, and folds the reading into
+    // the slot's end word: one atomic per workgroup, not per wave. The end atomics arrive together on one address and
+    // the launch cannot end before them: one per wave (753 at config 2) cost 6 us, one per workgroup 2. PH keeps the shape of its record: reading 3 is
+    // "result atomics complete" (the workgroup's, behind a barrier), and a relaxed returned ticket, which only this
+    // instantiation draws, lets the last workgroup store reading 4 and take the ticket back to zero.
+    if (form == SMALL_FORM_ACC) {  // uniform
+        if (PH) ph_loops = wall_clock64();
+        if (!PH && sl != 0) return;
+        if (prof && slices == 1) __syncthreads();  // uniform: acc_done is zero (else the LDS barrier above)
+        if (sl == 0 && live) {
+            const size_t at = (size_t)(c % acc_r) * lp + j;
+            __hip_atomic_fetch_max(skeys + at, top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_max(sfhi + at, st.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (st.y) __hip_atomic_fetch_max(sub + at, st.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (PH || prof) {  // uniform
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // the slice-0 wave that counts itself last reads the clock behind every other's completion
+            if (prof && sl == 0 && (threadIdx.x & 63u) == 0u && atomicAdd(&acc_done, 1u) == lp / 64u - 1u)
+                __hip_atomic_fetch_max(prof + 1, wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (PH) {
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                uint64_t* slot = phases + (size_t)c * 4;
+                slot[0] = ph_entry;
+                slot[1] = ph_loops;
+                slot[2] = wall_clock64();
+                const bool last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.y - 1u;
+                if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                slot[3] = last ? wall_clock64() : 0ull;
+            }
+        }
+        return;
+    }
     // One launch: fold into replica c % acc_r of the per-lane accumulators (skeys / sfhi / sub are then [acc_r][lp],
     // all zero between launches) by no-return agent-scope atomic maxima, each array lane-contiguous so that a wave's
     // instruction covers 512 / 256 contiguous bytes; idle lanes add nothing, sub only what is set. Then the arrival
@@ -437,11 +492,9 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
     // The finisher: one agent-scope acquire for the workgroup, then every accumulator word is read and reset in one
     // returned agent-scope exchange (atomics both sides of the hand-off), folded over the replicas per lane through
     // LDS, and every row takes its lane's result as k_small_finish writes it. The ticket goes back to zero too.
-    uint64_t t_begin = 0;
     if (threadIdx.x == 0) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (prof) t_begin = ~__hip_atomic_exchange(pbegin, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // also: every thread has read the verdict in lk[0]
@@ -522,10 +575,7 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
         if (threadIdx.x == 0) {
             const uint64_t t_end = wall_clock64();
             if (PH) phases[(size_t)c * 4 + 3] = t_end;
-            if (prof) {
-                __hip_atomic_fetch_add(prof, t_end - t_begin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_fetch_add(prof + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            if (prof) __hip_atomic_fetch_max(prof + 1, t_end, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -1404,9 +1454,11 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
     if (a.k != 1 || !a.fused || a.n_fast == 0 || a.n_fast != a.n_pods || lp > 256 || nc == 0 || nc > SMALL_MAX_CHUNKS ||
         (r0.n_chunks && (r0.chunk == 0 || r0.chunk > SMALL_MAX_CHUNK)) ||
         (r1.n_chunks && (r1.chunk == 0 || r1.chunk > SMALL_MAX_CHUNK)) || a.small_slices == 0 ||
-        a.small_slices * lp > SMALL_WG || !a.skeys || !a.sub || !a.sfhi || (!a.lane_of && !a.small_lanes) ||
-        (a.small_lanes && !a.small_replicas) || !a.out || !a.pstat ||
-        (a.small_replicas && !a.sticket) || (a.prof && (!a.small_replicas || a.ev_start || a.ev_stop)) || (a.phases && !a.prof))
+        a.small_slices * lp > SMALL_WG || !a.skeys || !a.sub || !a.sfhi ||
+        (!a.lane_of && !a.small_lanes && !a.small_acc) || ((a.small_lanes || a.small_acc) && !a.small_replicas) ||
+        (a.small_lanes && a.small_acc) || (!a.small_acc && (!a.out || !a.pstat || a.acc_zero_n)) ||
+        (a.acc_zero_n && !a.acc_zero) || (a.small_replicas && !a.sticket && (!a.small_acc || a.phases)) ||
+        (a.prof && (!a.small_replicas || a.ev_start || a.ev_stop)) || (a.phases && !a.prof))
         return hipErrorInvalidValue;
     dim3 grid(1, nc), block(lp * a.small_slices);
     const bool timed = a.ev_start && a.ev_stop;
@@ -1414,7 +1466,11 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
 #define KG_SMALL_ARGS                                                                                                 \
     a.nodes, a.zones, a.pods, a.n_fast, lp, r0.end, r1.end, r0.chunk, r1.chunk, r1.n_chunks, a.index_base, a.cfg,      \
         a.skeys, a.sub, a.sfhi, a.order, a.small_replicas, a.sticket, a.lane_of, a.n_rows, a.out, a.pstat, a.prof,    \
-        a.small_lanes ? SMALL_FORM_LANES : a.small_rows4 ? SMALL_FORM_ROWS4 : SMALL_FORM_ROWS
+        a.small_acc     ? SMALL_FORM_ACC                                                                             \
+        : a.small_lanes ? SMALL_FORM_LANES                                                                           \
+        : a.small_rows4 ? SMALL_FORM_ROWS4                                                                           \
+                        : SMALL_FORM_ROWS,                                                                           \
+        static_cast<uint4*>(a.acc_zero), a.acc_zero_n
 #define KG_SMALL_WG(PMV, WGV)                                                                                         \
     do {                                                                                                              \
         if (timed)                                                                                                    \

@@ -52,13 +52,14 @@ struct kg_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
     double prof_ms = 0.0;
     uint64_t prof_launches = 0;
-    // The one-launch small select times itself (k_select_small's prof): d_prof = {tick sum, launch count}
-    // of the device's wall clock, allocated and zeroed at the first such select and never reset; prof_seen = the words at
-    // the last kg_profile_read; prof_pending = launches handed d_prof since then; clock_khz = that clock's rate
-    // (hipDeviceAttributeWallClockRate; -1: not queried yet, 0: not available, the bound event pair stays).
+    // The one-launch small select times itself (k_select_small's prof): d_prof is a table of PROF_SLOTS
+    // slots {maximum of the entry-time complements, maximum of the end times} of the device's wall clock, allocated and
+    // zeroed at the first such select; every profiled launch gets the next slot, prof_pending = slots handed out since
+    // the table was last drained (prof_drain: kg_profile_read, or the select that finds it full); clock_khz = that
+    // clock's rate (hipDeviceAttributeWallClockRate; -1: not queried yet, 0: not available, the bound event pair stays).
+    static constexpr uint32_t PROF_SLOTS = 256;
     DevBuf<uint64_t> d_prof;
-    uint64_t prof_seen[2] = {0, 0};
-    uint64_t prof_pending = 0;
+    uint32_t prof_pending = 0;
     int clock_khz = -1;
     DevBuf<uint64_t> d_phases;  // KG_SMALL_PHASES: per-workgroup clock readings of one launch (measurement aid)
     int cus = -1;  // compute units of the device (device_cus), queried on first use
@@ -251,9 +252,17 @@ struct kg_pods {
     DevBuf<uint64_t> d_ipairs;       // pruned integer lanes: surviving (lane, record) pairs (LaunchSelect.ipairs)
     DevBuf<uint32_t> d_ipair_count;
     size_t ipairs_cap = 0;
-    // accumulators and ticket of the one-launch one-pod-block select: all zero between selects (ensure_sacc)
+    // accumulators and ticket of the one-launch one-pod-block select's finisher forms: all zero between selects
+    // (ensure_sacc)
     DevBuf<uint8_t> d_sacc;
     bool sacc_dirty = false;
+    // result accumulators of the form without a finisher (LaunchSelect.small_acc; ensure_acc): two parities of
+    // ACC_SLOTS x 16 bytes. The next such launch accumulates into parity acc_par, which is all zero, and zeroes the
+    // acc_dirty[acc_par ^ 1] 16-byte words that the launch before it left in the other one
+    static constexpr uint32_t ACC_SLOTS = 2048;  // replicas x lanes (whole waves) of one launch at most
+    DevBuf<uint8_t> d_acc;
+    bool acc_clear = false;  // both parities need the stream memset (a failed call)
+    uint32_t acc_par = 0, acc_dirty[2] = {0, 0};
     DevBuf<uint64_t> d_keys;
     uint32_t k_last = 0, kk_last = 0;
     PinnedBuf<uint64_t> h_keys;    // pinned download staging of the keys [cap][KG_TOPK_MAX]
@@ -264,18 +273,24 @@ struct kg_pods {
     // lane table that the select's batch was uploaded with, in h_in. d_keys / d_pstat then hold no result; kg_result_keys
     // and kg_result_status copy the lane tables into h_lres once per select (res_fetched) and gather on the host. The
     // next upload rewrites h_in: it drops a lane-form result (result_rows with k_last = 0).
+    // res_acc_r > 0 (with res_lanes): the accumulators are the result. Nothing was stored to d_lres; the readers copy
+    // the res_acc_r x res_lp x 16 bytes at res_acc (the launch's parity of d_acc) into h_lres and fold_acc turns them
+    // into the lane tables in place, once per select. res_stat_at = the status words' place in h_lres, in 64-bit words.
     // d_lres / h_lres are the last LRES_WORDS words of d_in / h_in, behind every region of pod_layout(cap): no upload
     // copies that far, and the batch has no allocation more than before.
-    static constexpr uint32_t LRES_LANES = 256, LRES_WORDS = LRES_LANES + LRES_LANES / 2;  // 64-bit words
+    static constexpr uint32_t LRES_LANES = 256, LRES_WORDS = 2 * ACC_SLOTS;  // 64-bit words
+    static_assert(LRES_WORDS >= LRES_LANES + LRES_LANES / 2 && ACC_SLOTS >= LRES_LANES, "the staging holds either form");
     uint64_t* d_lres = nullptr;
     uint64_t* h_lres = nullptr;
     bool res_lanes = false, res_fetched = false;
-    uint32_t res_lp = 0;
+    uint32_t res_lp = 0, res_acc_r = 0, res_stat_at = 0;
+    const uint8_t* res_acc = nullptr;
     const uint8_t* res_lane_of = nullptr;
     void result_rows(uint32_t k, uint32_t kk) {
         k_last = k;
         kk_last = kk;
         res_lanes = res_fetched = false;
+        res_acc_r = 0;
     }
     DevBuf<uint32_t> d_reason;  // replay: per pod OR of the filter status bits (kg_replay out_reason)
     // The row-list evaluators' scratch, grown on demand: no allocation on the steady path. Each buffer keeps its own
@@ -2873,12 +2888,18 @@ constexpr uint32_t SMALL_MIN_CHUNK = 8, SMALL_FILL_NUM = 63, SMALL_FILL_DEN = 64
 // config 4's 100,000 nodes at 145 lanes (1,667 chunks) 0.1350 / 0.1332 / 0.1333 / 0.1337 / 0.1349 / 0.1381 / 0.2615,
 // 0.1798. Hundreds of workgroups adding to one address cost under 0.001 ms; every replica more is read by the lone
 // finisher. KG_SMALL_REPLICAS (read per call) sets the count, also past the row gate: the tool and the tests.
+// Without a finisher (SMALL_ACC_REPLICAS; profiles/small_acc/replicas_config2.jsonl, config 2 at 145 lanes, ms per
+// select by replica count 1 / 2 / 4 / 8): 0.0156 / 0.0133 / 0.0122 / 0.0121-0.0122 without profiling, 0.0160 / 0.0143 /
+// 0.0142 / 0.0142 with it: contention at the end of the launch is on the critical path, and 8 is within the spread of 4.
 // Row gate (--rows, profiles/small_fused/rows_breakeven.jsonl; 145 lanes, one launch / two launches): 10,000 rows
 // 0.0180 / 0.0250 ms, 50,000 rows 0.0259 / 0.0248, 200,000 rows 0.0558 / 0.0252: the lone finisher writes n_rows x 12
 // bytes, the break-even interpolates to about 45,000 rows, the one launch is taken up to SMALL_FUSED_MAX_ROWS. The gate
 // is the row form's: a result kept per lane (lanes_ok below) stores no row, and its one launch measured 0.0149 / 0.0150 /
 // 0.0151 ms at 10,000 / 50,000 / 200,000 rows (tools/small_reader_ab.py, profiles/small_lanes/reader_ab.jsonl).
-constexpr uint32_t SMALL_REPLICAS = 4, SMALL_FUSED_MAX_ROWS = 32768;
+// The form without a finisher (lanes_ok and no KG_SMALL_FINISHER, read per call: the accumulators are the result,
+// DESIGN.md §4) has its own replica count, SMALL_ACC_REPLICAS: no finisher pays per replica, the reader folds them.
+// The count is capped by what the batch's accumulators and staging hold (kg_pods::ACC_SLOTS).
+constexpr uint32_t SMALL_REPLICAS = 4, SMALL_ACC_REPLICAS = 4, SMALL_FUSED_MAX_ROWS = 32768;
 static bool select_small(const kg_snap* s, LaunchSelect& a, bool lanes_ok) {
     if (a.k != 1 || !a.fused || a.n_fast == 0 || a.n_fast != a.n_pods || a.n_fast > 256) return false;
     if (std::getenv("KG_NO_SMALL_SELECT")) return false;
@@ -2932,14 +2953,17 @@ static bool select_small(const kg_snap* s, LaunchSelect& a, bool lanes_ok) {
     const uint32_t nc = r[0].n_chunks + r[1].n_chunks;
     a.small_replicas = 0;
     if (!std::getenv("KG_NO_SMALL_FUSED_FINISH")) {
-        uint32_t rep = lanes_ok || a.n_rows <= SMALL_FUSED_MAX_ROWS ? SMALL_REPLICAS : 0u;
+        const bool acc = lanes_ok && !std::getenv("KG_SMALL_FINISHER");
+        uint32_t rep = acc ? SMALL_ACC_REPLICAS : lanes_ok || a.n_rows <= SMALL_FUSED_MAX_ROWS ? SMALL_REPLICAS : 0u;
         if (const char* e = std::getenv("KG_SMALL_REPLICAS")) {  // also past the row gate
             unsigned v = 0;
             if (std::sscanf(e, "%u", &v) == 1 && v >= 1) rep = v;
         }
         a.small_replicas = std::min(rep, nc);  // more replicas than chunks: one chunk each
+        if (acc) a.small_replicas = std::min(a.small_replicas, kg_pods::ACC_SLOTS / lp);
+        a.small_acc = acc && a.small_replicas != 0;
     }
-    a.small_lanes = lanes_ok && a.small_replicas != 0;
+    a.small_lanes = lanes_ok && a.small_replicas != 0 && !a.small_acc;
     return true;
 }
 
@@ -2949,13 +2973,39 @@ static bool select_small(const kg_snap* s, LaunchSelect& a, bool lanes_ok) {
 // buffer is allocated or regrown, and again before the first select after one that returned an error (sacc_dirty);
 // k_select_small's finisher reads every accumulator word by an exchange with zero and stores zero to the ticket, so a
 // steady-state step zeroes nothing from the host. All words being zero, the next launch may lay the arrays out for
-// another replica or lane count.
+// another replica or lane count. The form without a finisher (LaunchSelect.small_acc) has accumulators of its own
+// under another rule (ensure_acc); a batch may switch between the forms from call to call.
 constexpr size_t SACC_HEAD = 128;
-static_assert((SMALL_BEGIN_WORD + 1) * sizeof(uint64_t) <= SACC_HEAD, "the begin word of a launch that times itself "
-              "(LaunchSelect.prof) lies on the ticket's line, under the same invariant");
 
-// The context's device-clock counters (kg_ctx.d_prof) for a profiled one-launch select; *out stays nullptr when the
-// device reports no wall clock rate: the caller then keeps the bound event pair.
+// Drains the context's device-clock slots (kg_ctx.d_prof): waits for the stream, adds end - begin of every slot handed
+// out since the last drain to prof_ms, counts them, and zeroes them again on the stream. A slot with a missing half
+// (its launch did not run to its end) is a KG_DEVICE_ERROR; the table is empty afterwards either way.
+static kg_status prof_drain(kg_ctx* ctx) {
+    const uint32_t n = ctx->prof_pending;
+    if (n == 0) return KG_OK;
+    ctx->prof_pending = 0;
+    // pageable staging, sized here: a profiled select allocates nothing but the table itself, once
+    std::vector<uint64_t> host(2 * (size_t)n);
+    uint64_t* h = host.data();
+    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_prof, 2 * sizeof(uint64_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_prof, 0, 2 * sizeof(uint64_t) * n, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t ticks = 0;
+    uint32_t bad = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t begin = ~h[2 * i], end = h[2 * i + 1];
+        if (h[2 * i] == 0 || end == 0 || end < begin) bad++;
+        else ticks += end - begin;
+    }
+    ctx->prof_ms += (double)ticks / (double)ctx->clock_khz;
+    ctx->prof_launches += n - bad;
+    if (bad) return fail(ctx, KG_DEVICE_ERROR, "device-timed selects: %u of %u launches left no complete bracket", bad, n);
+    return KG_OK;
+}
+
+// A slot of the context's device-clock table (kg_ctx.d_prof) for a profiled one-launch select; *out stays nullptr when
+// the device reports no wall clock rate: the caller then keeps the bound event pair. A full table is drained first. The
+// caller counts the slot (prof_pending) once its launch succeeded.
 static kg_status ensure_prof(kg_ctx* ctx, uint64_t** out) {
     *out = nullptr;
     if (ctx->clock_khz < 0) {
@@ -2965,23 +3015,27 @@ static kg_status ensure_prof(kg_ctx* ctx, uint64_t** out) {
     }
     if (ctx->clock_khz == 0) return KG_OK;
     if (!ctx->d_prof) {
-        HIP_TRY(ctx, ctx->d_prof.alloc(2));
-        const hipError_t e = hipMemsetAsync(ctx->d_prof, 0, 2 * sizeof(uint64_t), ctx->stream);
+        HIP_TRY(ctx, ctx->d_prof.alloc(2 * kg_ctx::PROF_SLOTS));
+        const hipError_t e = hipMemsetAsync(ctx->d_prof, 0, 2 * sizeof(uint64_t) * kg_ctx::PROF_SLOTS, ctx->stream);
         if (e != hipSuccess) {
             ctx->d_prof.reset();
             HIP_TRY(ctx, e);
         }
-        ctx->prof_seen[0] = ctx->prof_seen[1] = 0;
         ctx->prof_pending = 0;
     }
-    *out = ctx->d_prof;
+    if (ctx->prof_pending == kg_ctx::PROF_SLOTS) {
+        const kg_status st = prof_drain(ctx);
+        if (st != KG_OK) return st;
+    }
+    *out = ctx->d_prof + 2 * (size_t)ctx->prof_pending;
     return KG_OK;
 }
 
 // KG_SMALL_PHASES=<file> (read per call; measurement aid, tools/small_select_ab.py --phases): the one-launch select of
 // config 2's shape (all three plugins, the 1,024-thread variant) runs k_select_small's PH instantiation; after the
 // launch the stream is synchronised and one record is appended to the file: uint64 workgroup count, then four uint64
-// clock readings per workgroup (entry, loops done, ticket drawn, rows stored or 0). Other shapes ignore the switch.
+// clock readings per workgroup (entry, loops done, ticket drawn, rows stored or 0; without a finisher: entry, loops done,
+// result atomics complete, and the launch's end in the workgroup that was last, else 0). Other shapes ignore the switch.
 static const char* small_phases_file(const LaunchSelect& a, uint32_t lp) {
     const char* f = std::getenv("KG_SMALL_PHASES");
     if (!f || !*f || !a.small_replicas || (a.cfg.plugins & 7u) != 7u || a.small_slices * lp <= 512u) return nullptr;
@@ -3010,6 +3064,27 @@ static kg_status ensure_sacc(kg_pods* p, uint32_t replicas, uint32_t lp) {
     if (p->sacc_dirty) {
         HIP_TRY(ctx, hipMemsetAsync(p->d_sacc, 0, p->d_sacc.cap(), ctx->stream));
         p->sacc_dirty = false;
+    }
+    return KG_OK;
+}
+
+// The result accumulators of the form without a finisher (LaunchSelect.small_acc; kg_pods.d_acc). INVARIANT: when no
+// select runs on the batch, parity acc_par is all zero and the other one is zero past its first acc_dirty 16-byte
+// words. A launch accumulates into acc_par and zeroes the other parity's dirty words at its entry (same-stream order:
+// the launch that dirtied them, and the copy that read them, are through); select_local then swaps the parities. The
+// arrays of a launch start at the parity's base whatever its replica and lane counts, so the dirty words are a
+// prefix. The memset establishes the invariant at allocation and after a call that returned an error.
+static kg_status ensure_acc(kg_pods* p) {
+    kg_ctx* ctx = p->ctx;
+    constexpr size_t bytes = 2 * (size_t)kg_pods::ACC_SLOTS * 16;
+    if (!p->d_acc) {
+        HIP_TRY(ctx, p->d_acc.alloc(bytes));
+        p->acc_clear = true;
+    }
+    if (p->acc_clear) {
+        HIP_TRY(ctx, hipMemsetAsync(p->d_acc, 0, bytes, ctx->stream));
+        p->acc_clear = false;
+        p->acc_dirty[0] = p->acc_dirty[1] = 0;
     }
     return KG_OK;
 }
@@ -3094,10 +3169,20 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         // no expansion
         const uint32_t lp = (a.n_fast + 63) / 64 * 64;
         kg_status st;
-        if (a.small_replicas) {
+        const size_t acc_slots = (size_t)a.small_replicas * lp;  // small_acc: at most ACC_SLOTS (select_small)
+        if (a.small_acc) {
+            st = ensure_acc(p);
+            if (st != KG_OK) return st;
+            uint8_t* const mine = p->d_acc + (size_t)p->acc_par * kg_pods::ACC_SLOTS * 16;
+            a.skeys = reinterpret_cast<uint64_t*>(mine);
+            a.sfhi = reinterpret_cast<uint32_t*>(a.skeys + acc_slots);
+            a.sub = a.sfhi + acc_slots;
+            a.acc_zero = p->d_acc + (size_t)(p->acc_par ^ 1u) * kg_pods::ACC_SLOTS * 16;
+            a.acc_zero_n = p->acc_dirty[p->acc_par ^ 1u];
+        } else if (a.small_replicas) {
             st = ensure_sacc(p, a.small_replicas, lp);
             if (st != KG_OK) return st;
-            const size_t slots = (size_t)a.small_replicas * lp;
+            const size_t slots = acc_slots;
             a.sticket = reinterpret_cast<uint32_t*>(p->d_sacc.get());
             a.skeys = reinterpret_cast<uint64_t*>(p->d_sacc + SACC_HEAD);
             a.sfhi = reinterpret_cast<uint32_t*>(a.skeys + slots);
@@ -3120,9 +3205,9 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
             a.out = p->d_lres;
             a.pstat = reinterpret_cast<uint32_t*>(p->d_lres + lp);
         }
-        // kernel-time bracket (kg_profile_read). One launch: the kernel times itself with the device clock (a.prof; the
-        // begin word lies in the batch's accumulator buffer, so sacc_dirty clears it too), the launch is the plain one
-        // and the host only counts it, once it succeeded. Two launches, a device without a wall clock
+        // kernel-time bracket (kg_profile_read). One launch: the kernel times itself with the device clock (a.prof: a
+        // slot of the context's table, ensure_prof), the launch is the plain one and the host only counts the slot, once
+        // the launch succeeded. Two launches, a device without a wall clock
         // rate, or KG_PROFILE_BOUND_EVENTS (read per call: the tool and the tests compare both brackets): the launch
         // carries a pooled event pair itself (LaunchSelect.ev_start / ev_stop), nothing is recorded on the stream. The
         // pair goes on ev_live only once the launch took it; every failure hands it back to the pool
@@ -3131,6 +3216,11 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
         st = KG_OK;
         if (phases) {  // a launch of the measurement aid has no bracket: its tick pair is the scratch one in d_phases
             HIP_TRY(ctx, grow(ctx, ctx->d_phases, (size_t)nc * 4 + 2));
+            if (a.small_acc) {  // the ticket that only this instantiation draws: the finisher forms', zero between launches
+                st = ensure_sacc(p, 1, lp);
+                if (st != KG_OK) return st;
+                a.sticket = reinterpret_cast<uint32_t*>(p->d_sacc.get());
+            }
             a.phases = true;
             a.prof = ctx->d_phases;
         } else if (ctx->profiling && a.small_replicas && !std::getenv("KG_PROFILE_BOUND_EVENTS")) {
@@ -3141,6 +3231,8 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
             const hipError_t le = launch_select(a, ctx->stream);
             if (le != hipSuccess) {
                 bracket_drop(ctx, a.ev_start, a.ev_stop);
+                // the slot is not counted and goes to the next launch: zero, whatever this one wrote
+                if (a.prof && !phases) hipMemsetAsync(a.prof, 0, 2 * sizeof(uint64_t), ctx->stream);
                 st = fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR, "launch_select(a, ctx->stream): %s",
                           hipGetErrorString(le));
             } else if (a.prof && !phases) {
@@ -3151,13 +3243,22 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
             if (st == KG_OK && phases) st = small_phases_write(ctx, phases, nc);
         }
         // the batch claims a lane-form result only once its launch is on the stream (result_rows above: rows)
-        if (st == KG_OK && a.small_lanes) {
+        if (st == KG_OK && (a.small_lanes || a.small_acc)) {
             p->res_lanes = true;
             p->res_lp = lp;
+            p->res_stat_at = lp;
             p->res_lane_of = p->h_in.get() + (a.lane_of - p->d_in.get());
         }
+        if (st == KG_OK && a.small_acc) {  // the launch is on the stream: its parity is dirty, the other one clean
+            p->res_acc_r = a.small_replicas;
+            p->res_acc = reinterpret_cast<const uint8_t*>(a.skeys);
+            p->acc_dirty[p->acc_par] = (uint32_t)acc_slots;
+            p->acc_dirty[p->acc_par ^ 1u] = 0;
+            p->acc_par ^= 1u;
+        }
         // a failed call may have left a launch half done: the accumulators are zeroed again before the next one
-        if (st != KG_OK && a.small_replicas) p->sacc_dirty = true;
+        if (st != KG_OK && a.small_acc) p->acc_clear = true;
+        if (st != KG_OK && a.small_replicas && (!a.small_acc || phases)) p->sacc_dirty = true;
         return st;
     }
     HIP_TRY(ctx, hipMemsetAsync(p->d_pstat, 0, sizeof(uint32_t) * p->n, ctx->stream));
@@ -3236,14 +3337,46 @@ kg_status kg_eval_select(kg_snap* s, kg_pods* p, uint32_t k) {
 
 // A lane-form result (kg_pods.res_lanes) on the host: one copy of the res_lp keys and status words into the pinned
 // staging and the stream sync of every result read; the staging then serves every further read of the same select.
+// res_acc_r > 0: the copy is the launch's parity of the accumulators, res_acc_r x res_lp x 16 bytes, and fold_acc makes
+// the lane tables of it.
+static void fold_acc(kg_pods* p);
 static kg_status fetch_lanes(kg_pods* p) {
     kg_ctx* ctx = p->ctx;
-    if (!p->res_fetched)
-        HIP_TRY(ctx, hipMemcpyAsync(p->h_lres, p->d_lres, (sizeof(uint64_t) + sizeof(uint32_t)) * p->res_lp,
-                                    hipMemcpyDeviceToHost, ctx->stream));
+    if (!p->res_fetched) {
+        if (p->res_acc_r)
+            HIP_TRY(ctx, hipMemcpyAsync(p->h_lres, p->res_acc, (size_t)16 * p->res_acc_r * p->res_lp, hipMemcpyDeviceToHost,
+                                        ctx->stream));
+        else
+            HIP_TRY(ctx, hipMemcpyAsync(p->h_lres, p->d_lres, (sizeof(uint64_t) + sizeof(uint32_t)) * p->res_lp,
+                                        hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (!p->res_fetched && p->res_acc_r) fold_acc(p);
     p->res_fetched = true;
     return KG_OK;
+}
+
+// The staged accumulators of a select without a finisher, [r][lp] keys, [r][lp] fast-key high words, [r][lp] unsupported
+// bounds, become the lane tables in place: per lane the maximum over the replicas, and k_small_finish's status rule.
+// The keys of replica 0 are the key table; the status words take the place of replica 0's high words (res_stat_at).
+static void fold_acc(kg_pods* p) {
+    const uint32_t r = p->res_acc_r, lp = p->res_lp;
+    uint64_t* keys = p->h_lres;
+    uint32_t* fhi = reinterpret_cast<uint32_t*>(keys + (size_t)r * lp);
+    const uint32_t* ub = fhi + (size_t)r * lp;
+    for (uint32_t j = 0; j < lp; j++) {
+        uint64_t k = keys[j];
+        uint32_t f = fhi[j], u = ub[j];
+        for (uint32_t q = 1; q < r; q++) {
+            const size_t at = (size_t)q * lp + j;
+            k = std::max(k, keys[at]);
+            f = std::max(f, fhi[at]);
+            u = std::max(u, ub[at]);
+        }
+        keys[j] = k;
+        fhi[j] = u != 0u && u > f ? KG_ST_UNSUPPORTED : 0u;
+    }
+    p->res_stat_at = r * lp;
 }
 
 kg_status kg_result_keys(kg_pods* p, uint64_t* out) {
@@ -3297,7 +3430,7 @@ kg_status kg_result_status(kg_pods* p, uint32_t* out) {
     if (p->res_lanes) {
         kg_status st = fetch_lanes(p);
         if (st != KG_OK) return st;
-        const uint32_t* ls = reinterpret_cast<const uint32_t*>(p->h_lres + p->res_lp);
+        const uint32_t* ls = reinterpret_cast<const uint32_t*>(p->h_lres + p->res_stat_at);
         const uint8_t* lane = p->res_lane_of;
         for (uint32_t j = 0; j < p->n; j++) out[j] = ls[lane[j]];
         return KG_OK;
@@ -4655,21 +4788,9 @@ kg_status kg_profile_read(kg_ctx* ctx, double* total_ms, uint64_t* launches, int
         ctx->ev_free.push_back(e);
     }
     ctx->ev_live.clear();
-    // the one-launch small selects that timed themselves: the device's tick sum and launch count since the last read
-    if (ctx->prof_pending) {
-        uint64_t h[2] = {0, 0};
-        HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_prof, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        const uint64_t ticks = h[0] - ctx->prof_seen[0], n = h[1] - ctx->prof_seen[1], want = ctx->prof_pending;
-        ctx->prof_seen[0] = h[0];
-        ctx->prof_seen[1] = h[1];
-        ctx->prof_pending = 0;
-        if (n != want)
-            return fail(ctx, KG_DEVICE_ERROR, "device-timed selects: the device counted %llu launches, the host %llu",
-                        (unsigned long long)n, (unsigned long long)want);
-        ctx->prof_ms += (double)ticks / (double)ctx->clock_khz;
-        ctx->prof_launches += n;
-    }
+    // the one-launch small selects that timed themselves: their slots since the last drain
+    const kg_status dst = prof_drain(ctx);
+    if (dst != KG_OK) return dst;
     if (total_ms) *total_ms = ctx->prof_ms;
     if (launches) *launches = ctx->prof_launches;
     if (reset) {

@@ -7,7 +7,9 @@ launches. KG_SMALL_CHUNKS="c0,c1,copies" in the caller's environment sets the ge
     python tools/small_phases_by_chunk.py [--steps 20] [--all]
 
 Prints the loop time (entry to loops done) per storage class, the entry times, the workgroups that are through last,
-and with --all both series for every chunk (class-1 chunks first, as the kernel numbers them)."""
+and with --all both series for every chunk (class-1 chunks first, as the kernel numbers them). The third reading is
+"result atomics complete" in the default form, which has no finisher, and "ticket drawn" under KG_SMALL_FINISHER=1; the
+fourth is set in one workgroup, the last one through: the launch's end."""
 import argparse
 import os
 import sys
@@ -51,6 +53,9 @@ def main():
     entry = np.median(t[:, :, 0] - t0, axis=0) / 100
     own = np.median(t[:, :, 1] - t[:, :, 0], axis=0) / 100
     done = np.median(t[:, :, 1] - t0, axis=0) / 100
+    third = np.median(t[:, :, 2] - t0, axis=0) / 100
+    end = np.median(t[:, :, 3].max(axis=1) - t0[:, 0]) / 100
+    name3 = "ticket drawn" if os.environ.get("KG_SMALL_FINISHER") else "result atomics complete"
     # the kernel numbers the class-1 chunks first; how many there are follows from the class-1 chunk length
     setting = os.environ.get("KG_SMALL_CHUNKS")
     if not setting:
@@ -62,9 +67,11 @@ def main():
           (np.median(own[:nc1]), own[:nc1].max(), np.median(own[nc1:]), own[nc1:].max()))
     print("entry, class 1: median %.2f max %.2f; class 0: median %.2f max %.2f" %
           (np.median(entry[:nc1]), entry[:nc1].max(), np.median(entry[nc1:]), entry[nc1:].max()))
-    print("through last (chunk, entry, loops, loops done):")
+    print("%s: median %.2f max %.2f; end of launch %.2f, %.2f behind the slowest workgroup's loops" %
+          (name3, np.median(third), third.max(), end, end - done.max()))
+    print("through last (chunk, entry, loops, loops done, %s):" % name3)
     for c in np.argsort(-done)[:8]:
-        print("  %d %.2f %.2f %.2f" % (c, entry[c], own[c], done[c]))
+        print("  %d %.2f %.2f %.2f %.2f" % (c, entry[c], own[c], done[c], third[c]))
     if a.all:
         print("loops by chunk:", " ".join("%.1f" % x for x in own))
         print("entry by chunk:", " ".join("%.1f" % x for x in entry))

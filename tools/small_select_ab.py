@@ -25,6 +25,10 @@ keeps the event pair bound to its launch (KG_PROFILE_BOUND_EVENTS=1); every line
 --phases: where the one-launch kernel's time goes (KG_SMALL_PHASES: the kernel's instantiation that stores four clock
 readings per workgroup; config 2's shape only). One JSON line per snapshot: medians over workgroups and steps of the
 time from the launch's earliest entry to each workgroup's entry, loops done and ticket drawn, and to the finisher's end.
+In the default form (the accumulators are the result, no finisher) the third reading is "result atomics complete" and
+the fourth the same reading's successor in the workgroup that was last: the launch's end; the fields keep their names
+(ticket_* = atomics complete, finisher_end = end of launch). tail_us = end of launch - slowest workgroup's loops.
+--finisher: KG_SMALL_FINISHER=1 for the whole run, the lane form with its finisher (the form before; A/B yardstick).
 --shares "0,0.02,...": synth.mixed()'s nodes thinned to these F_BIG shares (every other node kept, the first F_BIG
 nodes up to the share), for the break-even of the F_BIG gate in select_small. KG_SMALL_ALLOW_BIG=1 (set here) lifts
 that gate so that both paths can be timed above it.
@@ -58,7 +62,12 @@ def main():
     ap.add_argument("--bracket", choices=["clock", "events"], default="clock",
                     help="with --profile: the one-launch select's bracket (device clock inside the launch / bound event pair)")
     ap.add_argument("--phases", action="store_true", help="per-workgroup phase times of the one-launch kernel")
+    ap.add_argument("--finisher", action="store_true", help="KG_SMALL_FINISHER=1: the lane form with its finisher")
     a = ap.parse_args()
+    if a.finisher:
+        os.environ["KG_SMALL_FINISHER"] = "1"
+    else:
+        os.environ.pop("KG_SMALL_FINISHER", None)
     if a.bracket == "events":
         os.environ["KG_PROFILE_BOUND_EVENTS"] = "1"
     else:
@@ -126,12 +135,13 @@ def main():
             at += 1 + 4 * nc
             t0 = t[:, 0].min()
             fin = t[t[:, 3] != 0]
-            assert len(fin) == 1, "one finisher per launch"
+            assert len(fin) == 1, "one finisher (or last workgroup) per launch"
             per.append(dict(workgroups=nc, entry=np.median(t[:, 0] - t0), entry_max=(t[:, 0] - t0).max(),
                             loops=np.median(t[:, 1] - t0), loops_max=(t[:, 1] - t0).max(),
                             ticket=np.median(t[:, 2] - t0), ticket_max=(t[:, 2] - t0).max(),
                             loops_own=np.median(t[:, 1] - t[:, 0]), ticket_own=np.median(t[:, 2] - t[:, 1]),
-                            finisher_ticket=fin[0, 2] - t0, finisher_end=fin[0, 3] - t0, finisher_own=fin[0, 3] - fin[0, 2]))
+                            finisher_ticket=fin[0, 2] - t0, finisher_end=fin[0, 3] - t0, finisher_own=fin[0, 3] - fin[0, 2],
+                            tail=fin[0, 3] - t[:, 1].max()))
         if not per:
             return None
         return {k + ("_us" if k != "workgroups" else ""): float(np.median([q[k] for q in per])) / (1.0 if k == "workgroups" else 100.0)
@@ -167,7 +177,7 @@ def main():
         keys = engine.eval_select(snap, batch, 1)
         keys0 = with_env("KG_NO_SMALL_SELECT", "1", lambda: engine.eval_select(snap, batch, 1))
         keys2 = with_env("KG_NO_SMALL_FUSED_FINISH", "1", lambda: engine.eval_select(snap, batch, 1))
-        head = {"nodes": name, "n_nodes": abi.table_len(nodes), "f_big_share": float(big.mean()), "pods": batch.n,
+        head = {"form": "finisher" if a.finisher else "default", "nodes": name, "n_nodes": abi.table_len(nodes), "f_big_share": float(big.mean()), "pods": batch.n,
                 "lanes": lanes[0], "fast_lanes": lanes[1], "steps": a.steps, "warmup": a.warmup,
                 "keys_equal": bool(np.array_equal(keys, keys0)), "keys_equal_two_launch": bool(np.array_equal(keys, keys2)),
                 "feasible_rows": int((keys != 0).sum())}
