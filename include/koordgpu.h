@@ -788,6 +788,120 @@ kg_status kg_eval_feasible(kg_snap* snap, kg_pods* pods, const uint32_t* rows, u
  * device does not follow. The symbol is new within ABI 14: a binding resolves it at load time. */
 kg_status kg_eval_offer_slots(kg_snap* snap, kg_pods* pods, const uint32_t* rows, uint32_t n_rows,
                               uint32_t* out_slots /* n_nodes */, uint32_t* out_status /* n_nodes, may be NULL */);
+/* ---- Preemption dry run (PostFilter) -------------------------------------------------------------------------------
+ * Resident pods of a snapshot: which pods run on each node, the table kg_eval_preempt removes victims from. One entry
+ * per running pod; the columns are what SelectVictimsOnNode reads of it. */
+#define KG_RES_MAX_PER_NODE 256   /* resident entries per node the device follows */
+#define KG_RES_PDBS 2             /* PodDisruptionBudgets one entry can name */
+#define KG_RES_NON_PREEMPTIBLE 0x1u /* extension.IsPodNonPreemptible / !IsPodPreemptible */
+#define KG_RES_NUMA_ALLOC 0x2u      /* the pod holds a cpuset or NUMA-zone allocation on the node
+                                       (nodenumaresource/preempt.go:227-237 getPodAllocated non-empty) */
+#define KG_RES_PDB_OVERFLOW 0x4u    /* the pod matches more than KG_RES_PDBS budgets */
+typedef struct kg_resident_columns {
+    const uint32_t* node;        /* snapshot position (index_base not added) */
+    const int32_t*  priority;    /* corev1helpers.PodPriority */
+    const int64_t*  start_time;  /* GetPodStartTime, unix seconds */
+    const int32_t*  group;       /* preemption group (the pod's quota name as an id), -1 = none */
+    const uint32_t* flags;       /* KG_RES_* */
+    const int32_t*  pdb[KG_RES_PDBS]; /* budget ids this pod counts against, -1 = unused. The host leaves out
+                                         budgets whose DisruptedPods hold the pod (preempt.go:248-252) */
+    const int64_t *req_cpu, *req_mem, *req_eph, *sc_req[KG_NSCALAR], *nz_cpu, *nz_mem; /* what NodeInfo.RemovePod subtracts */
+} kg_resident_columns;
+/* kg_snapshot_upload_residents replaces the whole table by the n rows of cols; kg_snapshot_update_residents replaces
+ * the lists of the n_nodes listed nodes (each at most once) by the n rows of cols, which name only those nodes (a
+ * listed node without a row ends up empty), and keeps every other list. Both copy; both bump the generation.
+ * Order: the library orders each node's entries by util.MoreImportantPod: higher priority first, then earlier start
+ * time; ties keep the order of the rows (of the call that supplied the list). Upstream's sort.Slice is not stable
+ * there: parity unpinned on ties. A victim's "position" in every output of kg_eval_preempt is its index in that
+ * ordered list; kg_snapshot_read_residents maps positions back to rows.
+ * The table is kept per snapshot position, so kg_snapshot_update_rows moving records does not disturb it.
+ * kg_snapshot_upload drops it. kg_assume*, kg_replay, kg_reserve and kg_batch_schedule do not touch it: the caller
+ * replaces a node's list after a bind. An update sends the new lists of its nodes alone (they are appended behind the
+ * table on the device; when that space is used up, one update lays the whole table out again).
+ * A node with more than KG_RES_MAX_PER_NODE entries is accepted and flagged: kg_eval_preempt reports
+ * KG_PREEMPT_UNSUPPORTED for it.
+ * KG_INVALID_ARG: a node >= n_nodes, a NULL column with n > 0, a pdb id < -1, (update) a row naming a node that is not
+ * listed, a node listed twice, no table uploaded yet. Nothing is changed then, nor by a call that fails on the device
+ * (KG_OOM, KG_DEVICE_ERROR): the table of before stays in place. */
+kg_status kg_snapshot_upload_residents(kg_snap* snap, const kg_resident_columns* cols, uint32_t n);
+kg_status kg_snapshot_update_residents(kg_snap* snap, const uint32_t* nodes, uint32_t n_nodes,
+                                       const kg_resident_columns* cols, uint32_t n);
+/* The table as the library ordered it: out_count[i] = entries of the node at snapshot position i (all of them, also
+ * beyond KG_RES_MAX_PER_NODE); out_row (may be NULL), node after node in position order, each node's entries in list
+ * order: the row of the upload / update call that supplied the entry. Sum of out_count entries. KG_INVALID_ARG
+ * without a table. */
+kg_status kg_snapshot_read_residents(kg_snap* snap, uint32_t* out_count /* n_nodes */, uint32_t* out_row);
+
+/* SelectVictimsOnNode (elasticquota/preempt.go:111-217, reservation/preemption.go:123-219) of each preemptor on
+ * every node of this snapshot: the 1 + V Filter runs per node of the PostFilter dry run (preemption.Evaluator.Preempt,
+ * elasticquota/plugin.go:608-619, reservation/preemption.go:102-116). Each row is one preemptor, evaluated on the
+ * snapshot as it stands, independently of the other rows. Per (preemptor, node), independently of every other node:
+ *  1. Potential victims: the node's entries with priority < row_priority[t]; with KG_PREEMPT_SKIP_NON_PREEMPTIBLE
+ *     without those flagged KG_RES_NON_PREEMPTIBLE; with KG_PREEMPT_SAME_GROUP only those whose group equals
+ *     row_group[t] (NULL: -1). None: KG_PREEMPT_NO_VICTIMS.
+ *  2. All of them are removed: the node's requested cpu / memory / ephemeral-storage / scalars, its non-zero requested
+ *     cpu / memory and its pod count drop by the entries' columns (NodeInfo.RemovePod; plain int64 subtraction). The
+ *     LoadAware bases, NUMA zone usage, cpusets and GPU minors stay the snapshot's: LoadAware has no AddPod / RemovePod
+ *     hook. The Filter word of the pair on that node is kg_eval_verify's, bit for bit, on a snapshot whose columns were
+ *     lowered so. Non-zero: KG_PREEMPT_NO_FIT with that word.
+ *  3. PDB split (filterPodsWithPDBViolation, preempt.go:224-269): the potential victims in list order, a fresh copy of
+ *     pdb_allowed per node; each budget an entry names is decremented, and the entry is violating when any of its
+ *     budgets went below 0. The order inside both groups is kept.
+ *  4. Reprieve: the violating group first, then the other, each from the most important entry: the entry is added
+ *     back and the word taken; 0: it stays; non-zero: it is removed again and is a victim (n_violating counts those of
+ *     the first group).
+ *  5. KG_PREEMPT_UNSUPPORTED, with n_victims = 0 (the host runs the reference on that node), when the node's list
+ *     overflowed, a potential victim has KG_RES_PDB_OVERFLOW, a potential victim has KG_RES_NUMA_ALLOC while
+ *     KG_PLUGIN_NUMA is on and the preemptor is not KG_POD_NUMA_SKIP (NodeNUMAResource's RemovePod then feeds a
+ *     preemptible state its Filter reads, nodenumaresource/preempt.go:165-217, which the device does not follow), or
+ *     any word taken on the node carries KG_ST_UNSUPPORTED.
+ * A node outside the preemptor's candidate node set (kg_pods_set_node_sets) is KG_PREEMPT_EXCLUDED: nothing is
+ * evaluated there. Precedence: EXCLUDED, the overflowed list (UNSUPPORTED), NO_VICTIMS, the victims' flags
+ * (UNSUPPORTED), the word after the removal (UNSUPPORTED / NO_FIT), the reprieve's words (UNSUPPORTED), CANDIDATE.
+ * Host score terms are ignored (Filter only). Nominated pods are not added (out of scope). */
+#define KG_PREEMPT_SKIP_NON_PREEMPTIBLE 0x1u /* reservation/preemption.go:154, elasticquota canPreempt :290 */
+#define KG_PREEMPT_SAME_GROUP 0x2u           /* canPreempt :309: victim.group == preemptor's group */
+typedef struct kg_preempt_node {   /* 32 bytes */
+    uint32_t status;       /* KG_ST_* word, see result */
+    uint8_t  result;       /* KG_PREEMPT_* */
+    uint8_t  pad_;
+    uint16_t n_victims;
+    uint16_t n_violating;  /* numViolatingVictim */
+    uint16_t n_potential;  /* potential victims (0 for EXCLUDED and for an overflowed list) */
+    int32_t  top_priority; /* highest priority among the victims */
+    int64_t  sum_priority; /* plain sum of the victims' priorities */
+    int64_t  top_start;    /* earliest start_time among the victims of top_priority */
+} kg_preempt_node;
+/* Every field but status, result and n_potential is 0 unless result is KG_PREEMPT_CANDIDATE with victims. */
+#define KG_PREEMPT_CANDIDATE 0u   /* Success: the victims are valid (n_victims may be 0: the pod fits as it is); status 0 */
+#define KG_PREEMPT_NO_VICTIMS 1u  /* no potential victim on the node (UnschedulableAndUnresolvable, preempt.go:150-153); status 0 */
+#define KG_PREEMPT_NO_FIT 2u      /* does not fit with every potential victim removed: status = that word */
+#define KG_PREEMPT_UNSUPPORTED 3u /* the host runs the reference there: status has KG_ST_UNSUPPORTED (the word that
+                                     carried it, or the bit alone) */
+#define KG_PREEMPT_EXCLUDED 4u    /* outside the preemptor's candidate node set: status = KG_ST_NODE_EXCLUDED, nothing evaluated */
+/*   rows     as kg_eval_diagnose: batch indices of the preemptors, repeats and any order allowed; NULL: every pod
+ *            (n_rows must equal the batch size).
+ *   row_priority[t]  the preemptor's priority (the pod columns carry none).
+ *   row_group[t]     its preemption group, NULL: -1 for all.
+ *   pdb_allowed[b], b < n_pdbs: PodDisruptionBudget.Status.DisruptionsAllowed of budget id b. Every pdb id of the
+ *            resident table must be < n_pdbs.
+ *   out[t * n_nodes + i], i the node's snapshot position (index_base is not added).
+ *   out_victims (may be NULL): [n_rows][n_nodes][KG_RES_MAX_PER_NODE / 32]; bit (k & 31) of word (k >> 5) is set iff
+ *            position k of the node's list is a victim; all 0 unless result is KG_PREEMPT_CANDIDATE.
+ * Per-node results do not depend on other nodes: the outputs of node shards concatenate. Synchronous like
+ * kg_eval_diagnose, with its precondition checks in its order. It changes no state of the snapshot (nor its
+ * generation), the batch's keys or kg_result_status. Every out entry is written. KG_INVALID_ARG: no resident table
+ * uploaded, out == NULL or row_priority == NULL with n_rows > 0 and n_nodes > 0, unknown flags, a row >= the batch
+ * size, rows == NULL with another n_rows, pdb_allowed == NULL with n_pdbs > 0, a pdb id of the table >= n_pdbs,
+ * candidate node sets over another node count. n_rows == 0 writes nothing; a snapshot of 0 nodes writes nothing.
+ * KG_UNSUPPORTED: a snapshot with config-5 tables (KG_PLUGIN_EXT): ElasticQuota's AddPod / RemovePod move
+ * postFilterState.used, and Reservation's and DeviceShare's hooks move state their Filters read, which the device does
+ * not follow. The symbols of this section are new within ABI 14: a binding resolves them at load time. */
+kg_status kg_eval_preempt(kg_snap* snap, kg_pods* pods, const uint32_t* rows, uint32_t n_rows,
+                          const int32_t* row_priority /* n_rows */, const int32_t* row_group /* n_rows or NULL */,
+                          const int32_t* pdb_allowed, uint32_t n_pdbs, uint32_t flags,
+                          kg_preempt_node* out /* n_rows * n_nodes */,
+                          uint32_t* out_victims /* n_rows * n_nodes * (KG_RES_MAX_PER_NODE / 32), may be NULL */);
 /* Sequential scheduling of pods[0..n) one at a time with Assume applied on the device between pods
  * (the reference's one-pod-per-cycle semantics). out_node[i] = global node index or -1 (no feasible node,
  * or the selected node's Reserve failed: KG_ST_NUMA_INSUF_* in out_reason).

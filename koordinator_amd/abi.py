@@ -150,6 +150,71 @@ _pu32 = C.POINTER(C.c_uint32)
 KG_EVAL_OFFER_SLOTS_ARGTYPES = [C.c_void_p, C.c_void_p, _pu32, C.c_uint32, _pu32, _pu32]
 
 
+# ---- the preemption dry run (kg_snapshot_upload_residents, kg_eval_preempt): constants of include/koordgpu.h
+KG_RES_MAX_PER_NODE = 256
+KG_RES_PDBS = 2
+KG_RES_NON_PREEMPTIBLE = 0x1
+KG_RES_NUMA_ALLOC = 0x2
+KG_RES_PDB_OVERFLOW = 0x4
+KG_PREEMPT_SKIP_NON_PREEMPTIBLE = 0x1
+KG_PREEMPT_SAME_GROUP = 0x2
+KG_PREEMPT_CANDIDATE, KG_PREEMPT_NO_VICTIMS, KG_PREEMPT_NO_FIT, KG_PREEMPT_UNSUPPORTED, KG_PREEMPT_EXCLUDED = range(5)
+KG_PREEMPT_MASK_WORDS = KG_RES_MAX_PER_NODE // 32
+
+
+class KgResidentColumns(C.Structure):
+    """kg_resident_columns: one row per running pod (koordinator_amd.preempt.build_residents builds the table)."""
+    _fields_ = [("node", _pu32), ("priority", C.POINTER(C.c_int32)), ("start_time", _p64),
+                ("group", C.POINTER(C.c_int32)), ("flags", _pu32), ("pdb", C.POINTER(C.c_int32) * KG_RES_PDBS),
+                ("req_cpu", _p64), ("req_mem", _p64), ("req_eph", _p64), ("sc_req", _p64 * KG_NSCALAR),
+                ("nz_cpu", _p64), ("nz_mem", _p64)]
+
+
+class KgPreemptNode(C.Structure):
+    """kg_preempt_node: SelectVictimsOnNode's outcome of one (preemptor, node) pair."""
+    _fields_ = [("status", C.c_uint32), ("result", C.c_uint8), ("pad_", C.c_uint8), ("n_victims", C.c_uint16),
+                ("n_violating", C.c_uint16), ("n_potential", C.c_uint16), ("top_priority", C.c_int32),
+                ("sum_priority", C.c_int64), ("top_start", C.c_int64)]
+
+
+# the same as a numpy record: engine.eval_preempt returns an array of it
+PREEMPT_NODE_DTYPE = np.dtype([("status", np.uint32), ("result", np.uint8), ("pad_", np.uint8), ("n_victims", np.uint16),
+                               ("n_violating", np.uint16), ("n_potential", np.uint16), ("top_priority", np.int32),
+                               ("sum_priority", np.int64), ("top_start", np.int64)])
+assert PREEMPT_NODE_DTYPE.itemsize == C.sizeof(KgPreemptNode) == 32
+
+RESIDENT_I64 = ["start_time", "req_cpu", "req_mem", "req_eph"] + [f"sc_req{i}" for i in range(KG_NSCALAR)] + ["nz_cpu", "nz_mem"]
+RESIDENT_I32 = ["priority", "group"] + [f"pdb{i}" for i in range(KG_RES_PDBS)]
+RESIDENT_U32 = ["node", "flags"]
+
+
+def empty_residents(n: int) -> "Table":
+    """A resident table of n rows: zeros, no group, no budgets."""
+    t = {k: np.zeros(n, np.int64) for k in RESIDENT_I64}
+    t.update({k: (np.zeros(n, np.int32) if k == "priority" else np.full(n, -1, np.int32)) for k in RESIDENT_I32})
+    t.update({k: np.zeros(n, np.uint32) for k in RESIDENT_U32})
+    return t
+
+
+def resident_columns(t: "Table") -> KgResidentColumns:
+    # converted copies where needed, kept alive on the struct: the caller's table is not rewritten
+    t = {k: np.ascontiguousarray(t[k], dt) for names, dt in ((RESIDENT_I64, np.int64), (RESIDENT_I32, np.int32),
+                                                              (RESIDENT_U32, np.uint32)) for k in names}
+    s = KgResidentColumns()
+    for k in ("start_time", "req_cpu", "req_mem", "req_eph", "nz_cpu", "nz_mem"):
+        setattr(s, k, t[k].ctypes.data_as(_p64))
+    for i in range(KG_NSCALAR):
+        s.sc_req[i] = t[f"sc_req{i}"].ctypes.data_as(_p64)
+    for i in range(KG_RES_PDBS):
+        s.pdb[i] = t[f"pdb{i}"].ctypes.data_as(C.POINTER(C.c_int32))
+    for k in ("priority", "group"):
+        setattr(s, k, t[k].ctypes.data_as(C.POINTER(C.c_int32)))
+    for k in ("node", "flags"):
+        setattr(s, k, t[k].ctypes.data_as(_pu32))
+    s._keep = t
+    return s
+
+
 class KgNodeSets(C.Structure):
     """kg_node_sets: per-pod candidate node sets (koordinator_amd.nodesets builds the arrays)."""
     _fields_ = [("pod_set", C.POINTER(C.c_int32)), ("bits", C.POINTER(C.c_uint32)), ("n_sets", C.c_uint32),

@@ -1,5 +1,6 @@
 // kg_rowfilter.h — the Filter status word of a (batch row, node record) pair for the row-list evaluators: kg_eval_diagnose
-// (kg_diag.hip), kg_eval_feasible (kg_feasible.hip) and kg_eval_offer_slots (kg_slots.hip). Internal to libkoordgpu.so.
+// (kg_diag.hip), kg_eval_feasible (kg_feasible.hip), kg_eval_offer_slots (kg_slots.hip) and kg_eval_preempt
+// (kg_preempt.hip). Internal to libkoordgpu.so.
 //
 // The word is kg_eval_verify's bit for bit: the plain plugin set evaluates a pair with eval_pair (filters only: no
 // score, no zone), the config-5 set with eval_pair_ext behind the ElasticQuota gate, and a record outside the pod's

@@ -36,6 +36,7 @@
 #include "kg_feasible.h"
 #include "kg_kernels.h"
 #include "kg_layout.h"
+#include "kg_preempt.h"
 #include "kg_scores.h"
 #include "kg_sets.h"
 #include "kg_slots.h"
@@ -187,6 +188,28 @@ struct kg_snap {
     DevBuf<uint32_t> d_part_rng;  // [KG_GPU_MAX_TABLES * 9]
     DevBuf<int64_t> d_binpack;    // [KG_GPU_MAX_TABLES][3][256]
     uint32_t n_gpu_tables = 0, n_gpu_parts = 0;
+    // Resident pods (kg_snapshot_upload_residents): per snapshot position the node's list in importance order (h_res)
+    // and, beside it, the row of the call that supplied each entry (h_res_row). The device holds the lists in
+    // d_res_ent behind an offset / count pair per position (records may move, positions do not; res_off / res_cnt are
+    // the host's copies). An upload lays the lists back to back and leaves a spare tail; an update appends the new
+    // lists of its nodes at res_used and points their offsets there, so it sends those lists alone and the old ones
+    // stay valid until the new offsets are in place. A full tail makes the update lay the table out afresh. A list
+    // longer than KG_RES_MAX_PER_NODE has no entries on the device (RES_OVERFLOW in its count).
+    std::vector<std::vector<ResEnt>> h_res;
+    std::vector<std::vector<uint32_t>> h_res_row;
+    std::vector<uint32_t> res_off, res_cnt;
+    size_t res_used = 0;  // entries of d_res_ent handed out (live lists and replaced ones)
+    bool has_res = false;
+    std::vector<int32_t> res_pdb;  // per position the largest budget id its list names, -1 = none
+    int32_t res_max_pdb = -1;      // the largest of them
+    DevBuf<ResEnt> d_res_ent;
+    DevBuf<uint32_t> d_res_off, d_res_cnt;
+    void drop_residents() {
+        h_res.clear();
+        h_res_row.clear();
+        has_res = false;
+        res_max_pdb = -1;
+    }
     bool ext() const { return (cfg.plugins & KG_PLUGIN_EXT) != 0; }
     ExtDev ext_dev() const {
         ExtDev e{};
@@ -303,6 +326,10 @@ struct kg_pods {
     DevBuf<uint32_t> d_feas_out;
     DevBuf<uint32_t> d_feas_count;
     DevBuf<uint32_t> d_slot_out;  // kg_eval_offer_slots: the [2][n_nodes] counts and status words in snapshot order
+    // kg_eval_preempt: the rows' priority, group and the allowed counts; the results and victim masks of one launch
+    DevBuf<int32_t> d_pre_args;
+    DevBuf<kg_preempt_node> d_pre_out;
+    DevBuf<uint32_t> d_pre_vic;
     DevBuf<DevSum> d_devsum;    // per record DevSum of the last config-5 select
     DevBuf<uint64_t> d_gz;      // gpu_zone_sum per (class-1 record, GPU request class) of the last config-5 select
     DevBuf<uint8_t> d_rcode;    // [kg_rsv_dev table][DEV_CLASSES]: GPU allocator outcome on the restore tables
@@ -1224,6 +1251,7 @@ kg_status kg_snapshot_upload(kg_snap* s, const kg_node_columns* cols) {
     s->uploaded = true;
     s->gen++;
     s->invalidate_saved();
+    s->drop_residents();
     return KG_OK;
 }
 
@@ -2344,6 +2372,279 @@ kg_status kg_eval_offer_slots(kg_snap* s, kg_pods* p, const uint32_t* rows, uint
     if (out_status)
         HIP_TRY(ctx, hipMemcpyAsync(out_status, d_status, sizeof(uint32_t) * s->n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return KG_OK;
+}
+
+// ---- resident pods and the preemption dry run: kg_snapshot_*_residents, kg_eval_preempt ---------------------------
+
+static kg_status check_residents(kg_snap* s, const kg_resident_columns* c, uint32_t n) {
+    kg_ctx* ctx = s->ctx;
+    if (n == 0) return KG_OK;
+    if (!c) return fail(ctx, KG_INVALID_ARG, "null resident columns with %u rows", n);
+    const void* cols[] = {c->node, c->priority, c->start_time, c->group, c->flags, c->pdb[0], c->pdb[1], c->req_cpu,
+                          c->req_mem, c->req_eph, c->sc_req[0], c->sc_req[1], c->nz_cpu, c->nz_mem};
+    static_assert(KG_RES_PDBS == 2 && KG_NSCALAR == 2, "the column list above");
+    for (const void* p : cols)
+        if (!p) return fail(ctx, KG_INVALID_ARG, "a resident column is NULL with %u rows", n);
+    for (uint32_t k = 0; k < n; k++) {
+        if (c->node[k] >= s->n) return fail(ctx, KG_INVALID_ARG, "resident row %u: node %u >= %u nodes", k, c->node[k], s->n);
+        for (int b = 0; b < KG_RES_PDBS; b++)
+            if (c->pdb[b][k] < -1) return fail(ctx, KG_INVALID_ARG, "resident row %u: pdb id %d", k, c->pdb[b][k]);
+    }
+    return KG_OK;
+}
+
+// The lists of one call: per node of `nodes` (each at most once) its rows of c ordered by util.MoreImportantPod
+// (stable: ties keep row order), as entries and as row numbers.
+struct ResLists {
+    std::vector<uint32_t> nodes;
+    std::vector<std::vector<ResEnt>> ent;
+    std::vector<std::vector<uint32_t>> row;
+};
+
+static ResLists build_residents(uint32_t n_nodes, const std::vector<uint32_t>& nodes, const kg_resident_columns* c, uint32_t n) {
+    ResLists out;
+    out.nodes = nodes;
+    out.ent.resize(nodes.size());
+    out.row.resize(nodes.size());
+    std::vector<uint32_t> slot(n_nodes, ~0u);
+    for (size_t t = 0; t < nodes.size(); t++) slot[nodes[t]] = (uint32_t)t;
+    for (uint32_t k = 0; k < n; k++) out.row[slot[c->node[k]]].push_back(k);
+    for (size_t t = 0; t < nodes.size(); t++) {
+        auto& rows = out.row[t];
+        std::stable_sort(rows.begin(), rows.end(), [c](uint32_t a, uint32_t b) {
+            return c->priority[a] != c->priority[b] ? c->priority[a] > c->priority[b] : c->start_time[a] < c->start_time[b];
+        });
+        out.ent[t].reserve(rows.size());
+        for (uint32_t k : rows) {
+            ResEnt e{};
+            e.req[0] = c->req_cpu[k];
+            e.req[1] = c->req_mem[k];
+            e.req[2] = c->req_eph[k];
+            e.req[3] = c->sc_req[0][k];
+            e.req[4] = c->sc_req[1][k];
+            e.nz_cpu = c->nz_cpu[k];
+            e.nz_mem = c->nz_mem[k];
+            e.start_time = c->start_time[k];
+            e.priority = c->priority[k];
+            e.group = c->group[k];
+            e.flags = c->flags[k];
+            for (int b = 0; b < KG_RES_PDBS; b++) e.pdb[b] = c->pdb[b][k];
+            out.ent[t].push_back(e);
+        }
+    }
+    return out;
+}
+
+static int32_t max_pdb_of(const std::vector<ResEnt>& l) {
+    int32_t m = -1;
+    for (const ResEnt& e : l)
+        for (int b = 0; b < KG_RES_PDBS; b++) m = std::max(m, e.pdb[b]);
+    return m;
+}
+
+// Both calls below build everything on the side (fresh device buffers, or the unused tail of d_res_ent) and change the
+// snapshot only after the last copy has completed: a failed call leaves the old table in place, host and device.
+
+// The whole table laid out afresh: the lists of nl replace those of its nodes, every other list is the snapshot's
+// (none when fresh).
+static kg_status relayout_residents(kg_snap* s, ResLists& nl, bool fresh) {
+    kg_ctx* ctx = s->ctx;
+    const uint32_t n = s->n;
+    std::vector<int32_t> slot(n, -1);
+    for (size_t t = 0; t < nl.nodes.size(); t++) slot[nl.nodes[t]] = (int32_t)t;
+    static const std::vector<ResEnt> none;
+    const auto list_of = [&](uint32_t i) -> const std::vector<ResEnt>& {
+        return slot[i] >= 0 ? nl.ent[slot[i]] : fresh ? none : s->h_res[i];
+    };
+    std::vector<uint32_t> off(std::max<uint32_t>(n, 1u)), cnt(std::max<uint32_t>(n, 1u));
+    std::vector<ResEnt> flat;
+    std::vector<int32_t> pdb(n, -1);
+    for (uint32_t i = 0; i < n; i++) {
+        const std::vector<ResEnt>& l = list_of(i);
+        off[i] = (uint32_t)flat.size();
+        pdb[i] = slot[i] >= 0 || fresh ? max_pdb_of(l) : s->res_pdb[i];
+        if (l.size() > KG_RES_MAX_PER_NODE) {
+            cnt[i] = RES_OVERFLOW;
+            continue;
+        }
+        cnt[i] = (uint32_t)l.size();
+        flat.insert(flat.end(), l.begin(), l.end());
+    }
+    if (flat.size() + flat.size() / 4 + 16384 > 0xFFFFFFFFull) return fail(ctx, KG_INVALID_ARG, "too many resident entries");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf<ResEnt> d_ent;
+    DevBuf<uint32_t> d_off, d_cnt;
+    HIP_TRY(ctx, d_ent.alloc(flat.size() + flat.size() / 4 + 16384));  // the tail the updates append to
+    HIP_TRY(ctx, d_off.alloc(off.size()));
+    HIP_TRY(ctx, d_cnt.alloc(cnt.size()));
+    if (!flat.empty())
+        HIP_TRY(ctx, hipMemcpyAsync(d_ent, flat.data(), sizeof(ResEnt) * flat.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_cnt, cnt.data(), sizeof(uint32_t) * cnt.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // also drains whatever read the old buffers
+    if (fresh) {
+        s->h_res.assign(n, {});
+        s->h_res_row.assign(n, {});
+    }
+    for (size_t t = 0; t < nl.nodes.size(); t++) {
+        s->h_res[nl.nodes[t]].swap(nl.ent[t]);
+        s->h_res_row[nl.nodes[t]].swap(nl.row[t]);
+    }
+    s->d_res_ent = std::move(d_ent);
+    s->d_res_off = std::move(d_off);
+    s->d_res_cnt = std::move(d_cnt);
+    s->res_off.swap(off);
+    s->res_cnt.swap(cnt);
+    s->res_used = flat.size();
+    s->res_pdb.swap(pdb);
+    s->res_max_pdb = n ? *std::max_element(s->res_pdb.begin(), s->res_pdb.end()) : -1;
+    s->has_res = true;
+    s->gen++;
+    return KG_OK;
+}
+
+kg_status kg_snapshot_upload_residents(kg_snap* s, const kg_resident_columns* cols, uint32_t n) {
+    if (!s) return KG_INVALID_ARG;
+    kg_ctx* ctx = s->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!s->uploaded) return fail(ctx, KG_INVALID_ARG, "snapshot not uploaded");
+    kg_status st = check_residents(s, cols, n);
+    if (st != KG_OK) return st;
+    std::vector<uint32_t> all(s->n);
+    for (uint32_t i = 0; i < s->n; i++) all[i] = i;
+    ResLists nl = build_residents(s->n, all, cols, n);
+    return relayout_residents(s, nl, true);
+}
+
+kg_status kg_snapshot_update_residents(kg_snap* s, const uint32_t* nodes, uint32_t n_nodes, const kg_resident_columns* cols,
+                                       uint32_t n) {
+    if (!s) return KG_INVALID_ARG;
+    kg_ctx* ctx = s->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!s->has_res) return fail(ctx, KG_INVALID_ARG, "no resident table to update (kg_snapshot_upload_residents)");
+    if (!nodes && n_nodes) return fail(ctx, KG_INVALID_ARG, "null node list");
+    kg_status st = check_residents(s, cols, n);
+    if (st != KG_OK) return st;
+    std::vector<uint8_t> listed(s->n, 0);
+    for (uint32_t k = 0; k < n_nodes; k++) {
+        if (nodes[k] >= s->n) return fail(ctx, KG_INVALID_ARG, "nodes[%u] = %u >= %u nodes", k, nodes[k], s->n);
+        if (listed[nodes[k]]) return fail(ctx, KG_INVALID_ARG, "node %u listed twice", nodes[k]);
+        listed[nodes[k]] = 1;
+    }
+    for (uint32_t k = 0; k < n; k++)
+        if (!listed[cols->node[k]])
+            return fail(ctx, KG_INVALID_ARG, "resident row %u names node %u, which is not listed", k, cols->node[k]);
+    ResLists nl = build_residents(s->n, std::vector<uint32_t>(nodes, nodes + n_nodes), cols, n);
+    // The new lists go behind everything handed out so far; the offsets and counts go into fresh buffers
+    std::vector<ResEnt> tail;
+    std::vector<uint32_t> off = s->res_off, cnt = s->res_cnt;
+    for (size_t t = 0; t < nl.nodes.size(); t++) {
+        const uint32_t i = nl.nodes[t];
+        off[i] = (uint32_t)(s->res_used + tail.size());
+        if (nl.ent[t].size() > KG_RES_MAX_PER_NODE) {
+            cnt[i] = RES_OVERFLOW;
+            continue;
+        }
+        cnt[i] = (uint32_t)nl.ent[t].size();
+        tail.insert(tail.end(), nl.ent[t].begin(), nl.ent[t].end());
+    }
+    if (s->res_used + tail.size() > s->d_res_ent.cap()) return relayout_residents(s, nl, false);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf<uint32_t> d_off, d_cnt;
+    HIP_TRY(ctx, d_off.alloc(off.size()));
+    HIP_TRY(ctx, d_cnt.alloc(cnt.size()));
+    if (!tail.empty())
+        HIP_TRY(ctx, hipMemcpyAsync(s->d_res_ent + s->res_used, tail.data(), sizeof(ResEnt) * tail.size(),
+                                    hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_cnt, cnt.data(), sizeof(uint32_t) * cnt.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t t = 0; t < nl.nodes.size(); t++) {
+        s->res_pdb[nl.nodes[t]] = max_pdb_of(nl.ent[t]);
+        s->h_res[nl.nodes[t]].swap(nl.ent[t]);
+        s->h_res_row[nl.nodes[t]].swap(nl.row[t]);
+    }
+    s->d_res_off = std::move(d_off);
+    s->d_res_cnt = std::move(d_cnt);
+    s->res_off.swap(off);
+    s->res_cnt.swap(cnt);
+    s->res_used += tail.size();
+    // a replaced list may have held the largest id
+    s->res_max_pdb = s->res_pdb.empty() ? -1 : *std::max_element(s->res_pdb.begin(), s->res_pdb.end());
+    s->gen++;
+    return KG_OK;
+}
+
+kg_status kg_snapshot_read_residents(kg_snap* s, uint32_t* out_count, uint32_t* out_row) {
+    if (!s) return KG_INVALID_ARG;
+    kg_ctx* ctx = s->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!s->has_res) return fail(ctx, KG_INVALID_ARG, "no resident table (kg_snapshot_upload_residents)");
+    if (!out_count && s->n) return fail(ctx, KG_INVALID_ARG, "null count output");
+    size_t at = 0;
+    for (uint32_t i = 0; i < s->n; i++) {
+        out_count[i] = (uint32_t)s->h_res_row[i].size();
+        if (out_row)
+            for (uint32_t row : s->h_res_row[i]) out_row[at++] = row;
+    }
+    return KG_OK;
+}
+
+kg_status kg_eval_preempt(kg_snap* s, kg_pods* p, const uint32_t* rows, uint32_t n_rows, const int32_t* row_priority,
+                          const int32_t* row_group, const int32_t* pdb_allowed, uint32_t n_pdbs, uint32_t flags,
+                          kg_preempt_node* out, uint32_t* out_victims) {
+    kg_status st = check_pair(s, p);
+    if (st != KG_OK) return st;
+    kg_ctx* ctx = s->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (flags & ~(KG_PREEMPT_SKIP_NON_PREEMPTIBLE | KG_PREEMPT_SAME_GROUP))
+        return fail(ctx, KG_INVALID_ARG, "preempt flags 0x%x", flags);
+    st = check_rows(p, rows, n_rows);
+    if (st != KG_OK) return st;
+    if ((!out || !row_priority) && n_rows && s->n) return fail(ctx, KG_INVALID_ARG, "null %s", out ? "row_priority" : "output");
+    if (!pdb_allowed && n_pdbs) return fail(ctx, KG_INVALID_ARG, "null pdb_allowed with %u budgets", n_pdbs);
+    // ElasticQuota's, Reservation's and DeviceShare's AddPod / RemovePod hooks move state the device does not follow
+    st = check_rowlist_snap(s, p, "preemption dry run on a snapshot with config-5 tables", false);
+    if (st != KG_OK) return st;
+    if (!s->has_res) return fail(ctx, KG_INVALID_ARG, "no resident table (kg_snapshot_upload_residents)");
+    if (s->res_max_pdb >= 0 && (uint32_t)s->res_max_pdb >= n_pdbs)
+        return fail(ctx, KG_INVALID_ARG, "the resident table names pdb id %d, n_pdbs is %u", s->res_max_pdb, n_pdbs);
+    if (n_rows == 0 || s->n == 0) return KG_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // Rows per launch: the scratch of one launch stays near 64 MiB (64 bytes per pair with the masks), grid.y in range
+    const size_t pair_bytes = sizeof(kg_preempt_node) + sizeof(uint32_t) * PREEMPT_MASK_WORDS;
+    const uint32_t per = (uint32_t)std::min<size_t>(std::min<uint32_t>(n_rows, 65535u),
+                                                    std::max<size_t>(1, ((size_t)64 << 20) / (pair_bytes * s->n)));
+    HIP_TRY(ctx, grow(ctx, p->d_pre_out, (size_t)per * s->n));
+    if (out_victims) HIP_TRY(ctx, grow(ctx, p->d_pre_vic, (size_t)per * s->n * PREEMPT_MASK_WORDS));
+    const size_t n_args = 2 * (size_t)n_rows + n_pdbs;
+    HIP_TRY(ctx, grow(ctx, p->d_pre_args, std::max<size_t>(n_args, 64)));
+    int32_t* d_prio = p->d_pre_args;
+    int32_t* d_group = d_prio + n_rows;
+    int32_t* d_allowed = d_group + n_rows;
+    HIP_TRY(ctx, hipMemcpyAsync(d_prio, row_priority, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, ctx->stream));
+    if (row_group) HIP_TRY(ctx, hipMemcpyAsync(d_group, row_group, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, ctx->stream));
+    if (n_pdbs) HIP_TRY(ctx, hipMemcpyAsync(d_allowed, pdb_allowed, sizeof(int32_t) * n_pdbs, hipMemcpyHostToDevice, ctx->stream));
+    RowFilter f;
+    st = stage_rowfilter(s, p, rows, n_rows, &f);
+    if (st != KG_OK) return st;
+    const ResDev res{s->d_res_ent, s->d_res_off, s->d_res_cnt};
+    const PreemptRows pr{d_prio, row_group ? d_group : nullptr, n_pdbs ? d_allowed : nullptr, n_pdbs, flags};
+    for (uint32_t base = 0; base < n_rows; base += per) {
+        const uint32_t m = std::min(per, n_rows - base);
+        const size_t pairs = (size_t)m * s->n;
+        uint32_t* d_vic = out_victims ? p->d_pre_vic.get() : nullptr;
+        st = bracketed(ctx, "kg_eval_preempt",
+                       [&] { return launch_preempt(f, res, pr, base, m, p->d_pre_out, d_vic, ctx->stream); });
+        if (st != KG_OK) return st;
+        HIP_TRY(ctx, hipMemcpyAsync(out + (size_t)base * s->n, p->d_pre_out, sizeof(kg_preempt_node) * pairs,
+                                    hipMemcpyDeviceToHost, ctx->stream));
+        if (out_victims)
+            HIP_TRY(ctx, hipMemcpyAsync(out_victims + (size_t)base * s->n * PREEMPT_MASK_WORDS, d_vic,
+                                        sizeof(uint32_t) * pairs * PREEMPT_MASK_WORDS, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the next launch rewrites the scratch
+    }
     return KG_OK;
 }
 

@@ -89,6 +89,15 @@ def lib():
     L.kg_eval_feasible.restype = st
     L.kg_eval_offer_slots.argtypes = abi.KG_EVAL_OFFER_SLOTS_ARGTYPES  # new within ABI 14: resolved at load time
     L.kg_eval_offer_slots.restype = st
+    # the preemption dry run: new within ABI 14, resolved at load time
+    L.kg_snapshot_upload_residents.argtypes = [vp, P(abi.KgResidentColumns), u32]
+    L.kg_snapshot_upload_residents.restype = st
+    L.kg_snapshot_update_residents.argtypes = [vp, P(u32), u32, P(abi.KgResidentColumns), u32]
+    L.kg_snapshot_update_residents.restype = st
+    L.kg_snapshot_read_residents.argtypes = [vp, P(u32), P(u32)]
+    L.kg_snapshot_read_residents.restype = st
+    L.kg_eval_preempt.argtypes = [vp, vp, P(u32), u32, P(i32), P(i32), P(i32), u32, u32, P(abi.KgPreemptNode), P(u32)]
+    L.kg_eval_preempt.restype = st
     L.kg_eval_select.argtypes = [vp, vp, u32]
     L.kg_eval_select.restype = st
     L.kg_result_keys.argtypes = [vp, P(u64)]
@@ -327,6 +336,36 @@ class Snapshot:
             C.cast(rsv.infos, C.POINTER(abi.KgRsvInfo)), rsv.n_infos,
             C.cast(rsv.devs, C.POINTER(abi.KgRsvDev)), rsv.n_devs), "kg_snapshot_update_views")
 
+    def upload_residents(self, residents: abi.Table):
+        """kg_snapshot_upload_residents: the running pods of every node (an abi.empty_residents-shaped table, one row
+        per pod; koordinator_amd.preempt.build_residents makes one). Replaces the whole table."""
+        n = abi.table_len(residents)
+        cols = abi.resident_columns(residents)
+        self.ctx.check(self.ctx.L.kg_snapshot_upload_residents(self.h, C.byref(cols), n), "kg_snapshot_upload_residents")
+
+    def update_residents(self, nodes, residents: abi.Table):
+        """kg_snapshot_update_residents: the lists of `nodes` (snapshot positions) replaced by the rows of `residents`,
+        which name only those nodes."""
+        nd = np.ascontiguousarray(np.asarray(nodes, np.uint32).reshape(-1))
+        n = abi.table_len(residents)
+        cols = abi.resident_columns(residents)
+        self.ctx.check(self.ctx.L.kg_snapshot_update_residents(
+            self.h, (nd if len(nd) else np.zeros(1, np.uint32)).ctypes.data_as(C.POINTER(C.c_uint32)), len(nd),
+            C.byref(cols), n), "kg_snapshot_update_residents")
+
+    def read_residents(self):
+        """kg_snapshot_read_residents: (count uint32[n_nodes], row uint32[sum of count]): per node the length of its
+        list, and node after node, in list (importance) order, the row of the upload / update call that supplied each
+        entry. Position k of node i in kg_eval_preempt's outputs is row[count[:i].sum() + k]."""
+        P = C.POINTER(C.c_uint32)
+        count = np.zeros(max(self.n, 1), np.uint32)
+        self.ctx.check(self.ctx.L.kg_snapshot_read_residents(self.h, count.ctypes.data_as(P), None),
+                       "kg_snapshot_read_residents")
+        row = np.zeros(max(int(count[:self.n].sum()), 1), np.uint32)
+        self.ctx.check(self.ctx.L.kg_snapshot_read_residents(self.h, count.ctypes.data_as(P), row.ctypes.data_as(P)),
+                       "kg_snapshot_read_residents")
+        return count[:self.n], row[:int(count[:self.n].sum())]
+
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
             self.ctx.L.kg_snapshot_destroy(self.h)
@@ -491,6 +530,34 @@ def eval_offer_slots(snap: Snapshot, pods: PodBatch, rows=None, status: bool = F
     snap.ctx.check(snap.ctx.L.kg_eval_offer_slots(snap.h, pods.h, rp, n_rows, slots.ctypes.data_as(P),
                                                   word.ctypes.data_as(P) if status else None), "kg_eval_offer_slots")
     return (slots[:snap.n], word[:snap.n]) if status else slots[:snap.n]
+
+
+def eval_preempt(snap: Snapshot, pods: PodBatch, rows, priority, group=None, pdb_allowed=None, flags: int = 0,
+                 victims: bool = False):
+    """kg_eval_preempt: SelectVictimsOnNode of every preemptor `rows` (batch indices; None = every pod) on every node.
+    priority: int32[n_rows], the preemptors' priorities; group: int32[n_rows] or None (-1 for all); pdb_allowed:
+    int32[n_pdbs], DisruptionsAllowed per budget id of the resident table; flags: KG_PREEMPT_*. Returns a record array
+    [n_rows, n_nodes] of abi.PREEMPT_NODE_DTYPE (status, result, n_victims, n_violating, n_potential, top_priority,
+    sum_priority, top_start); victims: also uint32[n_rows, n_nodes, KG_PREEMPT_MASK_WORDS], bit k = position k of the
+    node's list (Snapshot.read_residents) is a victim."""
+    n_rows, rp = _row_list(pods, rows)
+    i32p = C.POINTER(C.c_int32)
+    prio = np.ascontiguousarray(priority, np.int32).reshape(-1)
+    if len(prio) != n_rows:
+        raise ValueError(f"{len(prio)} priorities for {n_rows} rows")
+    grp = None if group is None else np.ascontiguousarray(group, np.int32).reshape(-1)
+    if grp is not None and len(grp) != n_rows:
+        raise ValueError(f"{len(grp)} groups for {n_rows} rows")
+    allowed = np.zeros(0, np.int32) if pdb_allowed is None else np.ascontiguousarray(pdb_allowed, np.int32).reshape(-1)
+    out = np.zeros((n_rows, snap.n), abi.PREEMPT_NODE_DTYPE)
+    vic = np.zeros((n_rows, snap.n, abi.KG_PREEMPT_MASK_WORDS), np.uint32) if victims else None
+    keep = lambda a: a if a.size else np.zeros(1, a.dtype)  # noqa: E731  (a pointer for an empty array)
+    snap.ctx.check(snap.ctx.L.kg_eval_preempt(
+        snap.h, pods.h, rp, n_rows, keep(prio).ctypes.data_as(i32p), None if grp is None else keep(grp).ctypes.data_as(i32p),
+        allowed.ctypes.data_as(i32p) if len(allowed) else None, len(allowed), int(flags),
+        keep(out).ctypes.data_as(C.POINTER(abi.KgPreemptNode)),
+        keep(vic).ctypes.data_as(C.POINTER(C.c_uint32)) if victims else None), "kg_eval_preempt")
+    return (out, vic) if victims else out
 
 
 def eval_select_async(snap: Snapshot, pods: PodBatch, k: int = 1):
