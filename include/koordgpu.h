@@ -1014,8 +1014,11 @@ kg_status kg_batch_schedule(kg_snap* snap, kg_pods* pods, const int32_t* plan_no
  * bracketed by HIP events on the launch stream. The one-launch top-1 select of one pod block times
  * itself with the device's wall clock instead (hipDeviceAttributeWallClockRate): its bracket runs from the first
  * workgroup's entry to the completion of the last result write, which leaves out the dispatch's launch ramp and
- * end-of-kernel release (a few microseconds). Each such launch fills a slot of a device table; kg_profile_read waits for
- * the brackets still outstanding and returns KG_DEVICE_ERROR when a launch left its slot incomplete. */
+ * end-of-kernel release (a few microseconds). Each such launch fills a region of a device pool, one pair of times per
+ * workgroup, which kg_profile_enable(ctx, 1) allocates on its first call (1 MiB of device memory on every context,
+ * whether or not it runs such a select): that call can therefore fail with KG_OOM or KG_DEVICE_ERROR, and profiling
+ * is then left off. kg_profile_read waits for the brackets still outstanding and returns KG_DEVICE_ERROR when a
+ * launch left its region incomplete. */
 kg_status kg_profile_enable(kg_ctx* ctx, int enable);
 kg_status kg_profile_read(kg_ctx* ctx, double* total_ms, uint64_t* launches, int reset);
 

@@ -85,11 +85,12 @@ struct LaunchSelect {
     // begin and ev_stop to the end of the kernel that finishes the step (hipExtLaunchKernelGGL), instead of the caller
     // recording events around it. Bound only when launch_select returns hipSuccess
     hipEvent_t ev_start, ev_stop;
-    // or (one launch only, never together with the pair) the kernel times itself with the device clock. prof is a slot
-    // of the launch's own, zero before it: prof[0] = maximum over the workgroups of ~(entry time), prof[1] = maximum of
-    // the end times (the finisher's last result store; small_acc: every slice-0 wave's last result atomic)
+    // or (one launch only, never together with the pair) the kernel times itself with the device clock. prof is a
+    // region of the launch's own, 16-byte aligned and zero before it: per workgroup c of the grid prof[2 * c] = its
+    // entry time and prof[2 * c + 1] = its end time (the finisher's last result store, zero in every other workgroup;
+    // small_acc: the workgroup's last result atomic), plain stores
     uint64_t* prof;
-    // measurement aid (KG_SMALL_PHASES): prof is a scratch pair of the launch's own, followed by [chunks][4] clock
+    // measurement aid (KG_SMALL_PHASES): prof is a scratch region of the launch's own, followed by [chunks][4] clock
     // readings per workgroup, see k_select_small
     bool phases;
 };
@@ -134,6 +135,9 @@ struct ExtVerifyDev {
 };
 
 hipError_t launch_select(const LaunchSelect& a, hipStream_t s);
+// Folds and re-zeroes the regions of n pending launches of the device-clock pool (LaunchSelect.prof): table[l] =
+// (workgroups << 32) | first pair of launch l, out[4 * l ..] = earliest entry, latest end, entry words set, end words set
+hipError_t launch_prof_fold(uint64_t* pool, const uint64_t* table, uint64_t* out, uint32_t n, hipStream_t s);
 
 // config-5 plugin set (kg_ext.hip)
 hipError_t launch_ext_gate(const PodsDev& pods, uint32_t n_pods, const ExtDev& e, uint32_t plugins, uint32_t* qst,

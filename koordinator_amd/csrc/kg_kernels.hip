@@ -286,16 +286,20 @@ __global__ __launch_bounds__(256) KG_SEL1_ATTR void k_select1(const NodeRec* __r
 // inline integer path fits without scratch) or 1024 (128 VGPRs: it spills; more copies per workgroup). The chunks are
 // dealt to the XCDs in contiguous runs (xcd_block; launch order measured the same).
 // prof (nullable; only with acc_r > 0): the launch times itself for kg_profile_read with the device-wide 100 MHz clock
-// (wall_clock64), so that the dispatch carries no event pair. prof is the launch's own slot of the context's table,
-// zero when the launch starts: {maximum of the complements of the entry times, maximum of the end times}. Thread 0 of
-// every workgroup folds the complement of its entry time into prof[0] (the maximum of the complements is the complement
-// of the earliest entry). The end: the finisher, once its result stores (rows or lanes) have completed; without a
-// finisher (SMALL_FORM_ACC) every slice-0 wave, once its own result atomics have completed. The host reads and
-// re-zeroes the slot. With prof == nullptr the kernel runs two uniform branches more and nothing else.
+// (wall_clock64), so that the dispatch carries no event pair. prof is the launch's own region of the context's pool,
+// zero when the launch starts: one 16-byte pair {entry time, end time} per workgroup, [2 * c] and [2 * c + 1], written
+// by plain stores of its own workgroup only: no two workgroups meet on an address, nothing serialises at the end of
+// the launch. Thread 0 keeps its entry time in LDS (prof_t0). The end: the finisher, once its result stores (rows or
+// lanes) have completed, stores its pair; every other workgroup of a finisher form stores its entry word alone and
+// leaves the end word zero. Without a finisher (SMALL_FORM_ACC) the slice-0 wave that counts itself last in acc_done,
+// behind the completion of every result atomic of the workgroup, stores the pair. The host folds the pairs (earliest
+// entry, latest end) and re-zeroes the region. With prof == nullptr the kernel runs two uniform branches more and
+// nothing else.
 // PH (KG_SMALL_PHASES, a measurement aid; off in every instantiation the library launches by default): prof is set and
-// the launch's own scratch pair, followed by four clock readings per workgroup that thread 0 stores: entry, loops done
+// a scratch region of the launch's own, followed by four clock readings per workgroup that thread 0 stores: entry, loops done
 // (after the slices met in LDS), ticket drawn (SMALL_FORM_ACC: result atomics complete) and, the finisher only
-// (SMALL_FORM_ACC: the workgroup that draws PH's last ticket; else zero), results stored.
+// (SMALL_FORM_ACC: the workgroup that draws PH's last ticket; else zero), results stored. Behind the [chunks][4]
+// readings follows one more per workgroup, "pod operands ready": thread 0's clock once its lane's PodF is converted.
 // form (uniform; acc_r > 0 only): what the finisher stores. SMALL_FORM_ROWS / SMALL_FORM_ROWS4: out / pstat of every
 // row through lane_of, one by one or four at a time (below). SMALL_FORM_LANES: out and pstat are per-lane tables of lp
 // entries and slice 0's thread j < n_lanes stores its lane's key and status word to out[j] / pstat[j]; lane_of and
@@ -323,14 +327,15 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
     __shared__ uint64_t lk[WG];
     __shared__ uint2 ls[WG];
     __shared__ uint32_t acc_done;  // prof in SMALL_FORM_ACC: slice-0 waves whose result atomics have completed
-    uint64_t ph_entry = 0, ph_loops = 0;
-    uint64_t* const phases = prof + 2;  // PH only
+    uint64_t ph_entry = 0, ph_loops = 0, ph_ops = 0;
+    __shared__ uint64_t prof_t0;   // prof: the workgroup's entry time
+    uint64_t* const phases = prof + 2 * (size_t)gridDim.y;  // PH only
     if (PH || prof) {  // uniform
         const uint64_t t_in = wall_clock64();
         if (PH) ph_entry = t_in;
         if (prof && threadIdx.x == 0) {
             acc_done = 0u;
-            __hip_atomic_fetch_max(prof, ~t_in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            prof_t0 = t_in;
         }
     }
     const uint32_t c = xcd_block().y, slices = blockDim.x / lp;
@@ -355,6 +360,11 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
     if (wlo + t < whi) big = ((uint32_t)nodes[wlo + t].v[N_FLAGS] & F_BIG) != 0;
     uint64_t bigm = __ballot(big);
     const PodF pf = to_podf(p, cfg);
+    if (PH) {  // "pod operands ready": the clock behind the lane's nine converted operands (order, load_pod, to_podf)
+        asm volatile("" ::"v"(pf.cpu), "v"(pf.mem), "v"(pf.eph), "v"(pf.sc0), "v"(pf.sc1), "v"(pf.nzc), "v"(pf.nzm),
+                     "v"(pf.e0), "v"(pf.e1));
+        ph_ops = wall_clock64();
+    }
     const KCfg cv = cfg_in_vgprs(cfg);
     const bool prod = __all(!live || fast_kind_match(FK_PROD, p)), batch = __all(!live || fast_kind_match(FK_BATCH, p));
     const uint32_t span = (whi - wlo + slices - 1) / slices;
@@ -429,15 +439,16 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
     // (below), into the parity that the launch before zeroed, and the workgroup is done: no ticket, no barrier, no
     // acquire, nothing read back. The other slices' waves have left after the LDS barrier. With prof every slice-0 wave
     // waits for its own atomics and counts itself in LDS (acc_done, no wave waits for another); the wave that counts
-    // last reads the clock, behind the completion of every result atomic of the workgroup, and folds the reading into
-    // the slot's end word: one atomic per workgroup, not per wave. The end atomics arrive together on one address and
-    // the launch cannot end before them: one per wave (753 at config 2) cost 6 us, one per workgroup 2. PH keeps the shape of its record: reading 3 is
+    // last reads the clock, behind the completion of every result atomic of the workgroup, and stores the workgroup's
+    // pair: one plain 16-byte store per workgroup to a word of its own. (End atomics on one shared word arrive together
+    // and the launch cannot end before them: one per wave, 753 at config 2, cost 6 us, one per workgroup 2; DESIGN.md
+    // §4.) PH keeps the shape of its record: reading 3 is
     // "result atomics complete" (the workgroup's, behind a barrier), and a relaxed returned ticket, which only this
     // instantiation draws, lets the last workgroup store reading 4 and take the ticket back to zero.
     if (form == SMALL_FORM_ACC) {  // uniform
         if (PH) ph_loops = wall_clock64();
         if (!PH && sl != 0) return;
-        if (prof && slices == 1) __syncthreads();  // uniform: acc_done is zero (else the LDS barrier above)
+        if (prof && slices == 1) __syncthreads();  // uniform: acc_done is zero, prof_t0 set (else the LDS barrier above)
         if (sl == 0 && live) {
             const size_t at = (size_t)(c % acc_r) * lp + j;
             __hip_atomic_fetch_max(skeys + at, top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -448,7 +459,7 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             // the slice-0 wave that counts itself last reads the clock behind every other's completion
             if (prof && sl == 0 && (threadIdx.x & 63u) == 0u && atomicAdd(&acc_done, 1u) == lp / 64u - 1u)
-                __hip_atomic_fetch_max(prof + 1, wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                *reinterpret_cast<ulonglong2*>(prof + 2 * (size_t)c) = make_ulonglong2(prof_t0, wall_clock64());
         }
         if (PH) {
             __syncthreads();
@@ -460,6 +471,7 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
                 const bool last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.y - 1u;
                 if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 slot[3] = last ? wall_clock64() : 0ull;
+                phases[4 * (size_t)gridDim.y + c] = ph_ops;
             }
         }
         return;
@@ -487,8 +499,12 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
         slot[1] = ph_loops;
         slot[2] = wall_clock64();
         slot[3] = 0;
+        phases[4 * (size_t)gridDim.y + c] = ph_ops;
     }
-    if (lk[0] == 0ull) return;  // uniform
+    if (lk[0] == 0ull) {  // uniform
+        if (prof && threadIdx.x == 0) prof[2 * (size_t)c] = prof_t0;
+        return;
+    }
     // The finisher: one agent-scope acquire for the workgroup, then every accumulator word is read and reset in one
     // returned agent-scope exchange (atomics both sides of the hand-off), folded over the replicas per lane through
     // LDS, and every row takes its lane's result as k_small_finish writes it. The ticket goes back to zero too.
@@ -575,7 +591,7 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
         if (threadIdx.x == 0) {
             const uint64_t t_end = wall_clock64();
             if (PH) phases[(size_t)c * 4 + 3] = t_end;
-            if (prof) __hip_atomic_fetch_max(prof + 1, t_end, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (prof) *reinterpret_cast<ulonglong2*>(prof + 2 * (size_t)c) = make_ulonglong2(prof_t0, t_end);
         }
     }
 }
@@ -785,6 +801,58 @@ hipError_t launch_expand_keys(const uint32_t* rep, uint32_t n, uint32_t k, uint6
         k_expand_keys<1><<<dim3((n + 255) / 256), 256, 0, s>>>(rep, n, out, pstat);
     else
         k_expand_keys<KG_TOPK_MAX><<<dim3((n * (KG_TOPK_MAX / 2) + 255) / 256), 256, 0, s>>>(rep, n, out, pstat);
+    return hipGetLastError();
+}
+
+// The drain of the device-clock pool (k_select_small's prof; prof_drain in kg_runtime.cpp): workgroup l folds the
+// region of pending launch l, table[l] = (workgroups << 32) | first pair, into out[4 * l ..]: the earliest non-zero
+// entry time (~0 when there is none), the latest end time, and how many entry and end words were set; every pair goes
+// back to zero. The host then copies 32 bytes per launch, not 16 per workgroup.
+constexpr uint32_t PROF_FOLD_WG = 256;
+__global__ __launch_bounds__(PROF_FOLD_WG) void k_prof_fold(uint64_t* __restrict__ pool, const uint64_t* __restrict__ table,
+                                                            uint64_t* __restrict__ out) {
+    __shared__ uint64_t lb[PROF_FOLD_WG], le[PROF_FOLD_WG];
+    __shared__ uint32_t ln[PROF_FOLD_WG], lm[PROF_FOLD_WG];
+    const uint64_t t = table[blockIdx.x];
+    const uint32_t first = (uint32_t)t, nc = (uint32_t)(t >> 32);
+    ulonglong2* const pairs = reinterpret_cast<ulonglong2*>(pool) + first;
+    uint64_t begin = ~0ull, end = 0;
+    uint32_t entries = 0, ends = 0;
+    for (uint32_t c = threadIdx.x; c < nc; c += PROF_FOLD_WG) {
+        const ulonglong2 p = pairs[c];
+        pairs[c] = make_ulonglong2(0ull, 0ull);
+        entries += p.x != 0;
+        ends += p.y != 0;
+        begin = p.x != 0 && p.x < begin ? p.x : begin;
+        end = p.y > end ? p.y : end;
+    }
+    lb[threadIdx.x] = begin;
+    le[threadIdx.x] = end;
+    ln[threadIdx.x] = entries;
+    lm[threadIdx.x] = ends;
+    __syncthreads();
+    for (uint32_t h = PROF_FOLD_WG / 2; h > 0; h >>= 1) {
+        if (threadIdx.x < h) {
+            const uint64_t b2 = lb[threadIdx.x + h], e2 = le[threadIdx.x + h];
+            lb[threadIdx.x] = b2 < lb[threadIdx.x] ? b2 : lb[threadIdx.x];
+            le[threadIdx.x] = e2 > le[threadIdx.x] ? e2 : le[threadIdx.x];
+            ln[threadIdx.x] += ln[threadIdx.x + h];
+            lm[threadIdx.x] += lm[threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        uint64_t* const o = out + 4 * (size_t)blockIdx.x;
+        o[0] = lb[0];
+        o[1] = le[0];
+        o[2] = ln[0];
+        o[3] = lm[0];
+    }
+}
+
+hipError_t launch_prof_fold(uint64_t* pool, const uint64_t* table, uint64_t* out, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    k_prof_fold<<<dim3(n), PROF_FOLD_WG, 0, s>>>(pool, table, out);
     return hipGetLastError();
 }
 
@@ -1446,7 +1514,7 @@ static void select_fast(const LaunchSelect& a, const SelectRange& r, hipStream_t
 // hipExtLaunchKernelGGL, which binds the events to the dispatch's own begin and end timestamps: the start event to
 // k_select_small, the stop event to the kernel that ends the step. Nothing is recorded on the stream. Without them the
 // launch is the plain <<<>>> one. a.prof (one launch only): the kernel times itself, plain launch, no events. a.phases
-// (a.prof is then the launch's scratch pair in front of the readings): the PH instantiation, which exists for the plugin mask and launch bound of config 2 only.
+// (a.prof is then the launch's scratch region in front of the readings): the PH instantiation, which exists for the plugin mask and launch bound of config 2 only.
 static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
     const uint32_t lp = (a.n_fast + 63) / 64 * 64;
     const SelectRange &r0 = a.range[0], &r1 = a.range[1];

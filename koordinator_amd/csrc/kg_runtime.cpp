@@ -53,14 +53,26 @@ struct kg_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
     double prof_ms = 0.0;
     uint64_t prof_launches = 0;
-    // The one-launch small select times itself (k_select_small's prof): d_prof is a table of PROF_SLOTS
-    // slots {maximum of the entry-time complements, maximum of the end times} of the device's wall clock, allocated and
-    // zeroed at the first such select; every profiled launch gets the next slot, prof_pending = slots handed out since
-    // the table was last drained (prof_drain: kg_profile_read, or the select that finds it full); clock_khz = that
-    // clock's rate (hipDeviceAttributeWallClockRate; -1: not queried yet, 0: not available, the bound event pair stays).
-    static constexpr uint32_t PROF_SLOTS = 256;
+    // The one-launch small select times itself (k_select_small's prof): d_prof is a pool of PROF_PAIRS
+    // 16-byte pairs {entry time, end time} of the device's wall clock, allocated and zeroed by kg_profile_enable (or
+    // the first such select), followed by the drain's launch table (PROF_SLOTS words) and its output (4 words per
+    // launch). Every profiled launch gets the next region of the pool, one pair per workgroup, and an entry of the
+    // launch table (prof_launch: workgroups, and whether every workgroup stores an end time; prof_table: what the
+    // drain's kernel reads); prof_pending = launches and prof_used = pairs handed out since the pool was last drained
+    // (prof_drain: kg_profile_read, or the select that finds the table or the pool full); prof_host = the drain's
+    // pageable staging; clock_khz = that clock's rate (hipDeviceAttributeWallClockRate; -1: not queried yet, 0: not
+    // available, the bound event pair stays).
+    static constexpr uint32_t PROF_SLOTS = 256;     // launches between two drains
+    static constexpr uint32_t PROF_PAIRS = 65536;   // workgroups between two drains: 1 MiB
+    static_assert(PROF_PAIRS >= SMALL_MAX_CHUNKS, "the largest one-launch grid fits in an empty pool");
+    struct ProfLaunch {
+        uint32_t nc;
+        bool all_end;
+    };
     DevBuf<uint64_t> d_prof;
-    uint32_t prof_pending = 0;
+    uint64_t prof_table[PROF_SLOTS], prof_host[4 * PROF_SLOTS];
+    ProfLaunch prof_launch[PROF_SLOTS];
+    uint32_t prof_pending = 0, prof_used = 0;
     int clock_khz = -1;
     DevBuf<uint64_t> d_phases;  // KG_SMALL_PHASES: per-workgroup clock readings of one launch (measurement aid)
     int cus = -1;  // compute units of the device (device_cus), queried on first use
@@ -3278,24 +3290,31 @@ static bool select_small(const kg_snap* s, LaunchSelect& a, bool lanes_ok) {
 // under another rule (ensure_acc); a batch may switch between the forms from call to call.
 constexpr size_t SACC_HEAD = 128;
 
-// Drains the context's device-clock slots (kg_ctx.d_prof): waits for the stream, adds end - begin of every slot handed
-// out since the last drain to prof_ms, counts them, and zeroes them again on the stream. A slot with a missing half
-// (its launch did not run to its end) is a KG_DEVICE_ERROR; the table is empty afterwards either way.
+// Drains the context's device-clock pool (kg_ctx.d_prof): k_prof_fold folds the region of every launch since the last
+// drain on the stream (begin = the earliest entry over its workgroups, end = the latest end, and how many of each were
+// set) and zeroes the used pairs again; the host uploads the launch table, copies 32 bytes per launch back, waits for
+// the stream, adds end - begin to prof_ms and counts the launches. A launch with a missing word (an entry; an end where
+// every workgroup stores one, else all ends: it did not run to its end) is a KG_DEVICE_ERROR; the pool is empty
+// afterwards either way. Copying the pairs themselves (1 MB of pageable memory per 256 selects of config 2's 251
+// workgroups) cost bench.py's loop its gain once it ran past the table (profiles/small_tail/bench_steps.jsonl).
 static kg_status prof_drain(kg_ctx* ctx) {
     const uint32_t n = ctx->prof_pending;
     if (n == 0) return KG_OK;
     ctx->prof_pending = 0;
-    // pageable staging, sized here: a profiled select allocates nothing but the table itself, once
-    std::vector<uint64_t> host(2 * (size_t)n);
-    uint64_t* h = host.data();
-    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_prof, 2 * sizeof(uint64_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_prof, 0, 2 * sizeof(uint64_t) * n, ctx->stream));
+    ctx->prof_used = 0;
+    uint64_t* const d_table = ctx->d_prof + 2 * (size_t)kg_ctx::PROF_PAIRS;
+    uint64_t* const d_out = d_table + kg_ctx::PROF_SLOTS;
+    const uint64_t* h = ctx->prof_host;
+    HIP_TRY(ctx, hipMemcpyAsync(d_table, ctx->prof_table, sizeof(uint64_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, launch_prof_fold(ctx->d_prof, d_table, d_out, n, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->prof_host, d_out, 4 * sizeof(uint64_t) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t ticks = 0;
     uint32_t bad = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint64_t begin = ~h[2 * i], end = h[2 * i + 1];
-        if (h[2 * i] == 0 || end == 0 || end < begin) bad++;
+    for (uint32_t i = 0; i < n; i++, h += 4) {
+        const kg_ctx::ProfLaunch& l = ctx->prof_launch[i];
+        const uint64_t begin = h[0], end = h[1], entries = h[2], ends = h[3];
+        if (entries != l.nc || ends < (l.all_end ? l.nc : 1u) || end < begin) bad++;
         else ticks += end - begin;
     }
     ctx->prof_ms += (double)ticks / (double)ctx->clock_khz;
@@ -3304,39 +3323,59 @@ static kg_status prof_drain(kg_ctx* ctx) {
     return KG_OK;
 }
 
-// A slot of the context's device-clock table (kg_ctx.d_prof) for a profiled one-launch select; *out stays nullptr when
-// the device reports no wall clock rate: the caller then keeps the bound event pair. A full table is drained first. The
-// caller counts the slot (prof_pending) once its launch succeeded.
-static kg_status ensure_prof(kg_ctx* ctx, uint64_t** out) {
-    *out = nullptr;
+// The pool itself, with the drain's table and output behind it, allocated and zeroed once per context: by
+// kg_profile_enable, so that no timed loop that follows it pays for the allocation (profiles/small_acc/ recorded 0.0025
+// ms per step of a 20-step loop), or by the first profiled select. d_prof stays empty on a device that reports no wall
+// clock rate.
+static kg_status prof_pool(kg_ctx* ctx) {
     if (ctx->clock_khz < 0) {
         int khz = 0;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ctx->device) != hipSuccess) khz = 0;
         ctx->clock_khz = khz > 0 ? khz : 0;
     }
-    if (ctx->clock_khz == 0) return KG_OK;
-    if (!ctx->d_prof) {
-        HIP_TRY(ctx, ctx->d_prof.alloc(2 * kg_ctx::PROF_SLOTS));
-        const hipError_t e = hipMemsetAsync(ctx->d_prof, 0, 2 * sizeof(uint64_t) * kg_ctx::PROF_SLOTS, ctx->stream);
-        if (e != hipSuccess) {
-            ctx->d_prof.reset();
-            HIP_TRY(ctx, e);
-        }
-        ctx->prof_pending = 0;
+    if (ctx->clock_khz == 0 || ctx->d_prof) return KG_OK;
+    HIP_TRY(ctx, ctx->d_prof.alloc(2 * (size_t)kg_ctx::PROF_PAIRS + 5 * (size_t)kg_ctx::PROF_SLOTS));
+    const hipError_t e = hipMemsetAsync(ctx->d_prof, 0, 2 * sizeof(uint64_t) * kg_ctx::PROF_PAIRS, ctx->stream);
+    if (e != hipSuccess) {
+        ctx->d_prof.reset();
+        HIP_TRY(ctx, e);
     }
-    if (ctx->prof_pending == kg_ctx::PROF_SLOTS) {
+    ctx->prof_pending = ctx->prof_used = 0;
+    return KG_OK;
+}
+
+// A region of nc pairs of the context's device-clock pool (kg_ctx.d_prof) for a profiled one-launch select of nc
+// workgroups; *out stays nullptr when the device reports no wall clock rate: the caller then keeps the bound event
+// pair, as it would for a region that does not fit in an empty pool (no launch has one: select_small keeps nc at most
+// SMALL_MAX_CHUNKS, asserted against PROF_PAIRS). A full launch table, or a pool without nc free pairs, is drained
+// first. The caller counts the region (prof_take) once its launch succeeded.
+static kg_status ensure_prof(kg_ctx* ctx, uint32_t nc, uint64_t** out) {
+    *out = nullptr;
+    if (nc == 0 || nc > kg_ctx::PROF_PAIRS) return KG_OK;
+    const kg_status pst = prof_pool(ctx);
+    if (pst != KG_OK || !ctx->d_prof) return pst;
+    if (ctx->prof_pending == kg_ctx::PROF_SLOTS || ctx->prof_used + nc > kg_ctx::PROF_PAIRS) {
         const kg_status st = prof_drain(ctx);
         if (st != KG_OK) return st;
     }
-    *out = ctx->d_prof + 2 * (size_t)ctx->prof_pending;
+    *out = ctx->d_prof + 2 * (size_t)ctx->prof_used;
     return KG_OK;
+}
+
+// The launch that ensure_prof gave a region is on the stream: its nc pairs and its table entry are taken.
+static void prof_take(kg_ctx* ctx, uint32_t nc, bool all_end) {
+    ctx->prof_table[ctx->prof_pending] = ((uint64_t)nc << 32) | ctx->prof_used;
+    ctx->prof_launch[ctx->prof_pending++] = {nc, all_end};
+    ctx->prof_used += nc;
 }
 
 // KG_SMALL_PHASES=<file> (read per call; measurement aid, tools/small_select_ab.py --phases): the one-launch select of
 // config 2's shape (all three plugins, the 1,024-thread variant) runs k_select_small's PH instantiation; after the
 // launch the stream is synchronised and one record is appended to the file: uint64 workgroup count, then four uint64
 // clock readings per workgroup (entry, loops done, ticket drawn, rows stored or 0; without a finisher: entry, loops done,
-// result atomics complete, and the launch's end in the workgroup that was last, else 0). Other shapes ignore the switch.
+// result atomics complete, and the launch's end in the workgroup that was last, else 0). A fifth reading per workgroup,
+// "pod operands ready", goes to <file>.ops in records of its own (workgroup count, then one reading each). Other shapes
+// ignore the switch.
 static const char* small_phases_file(const LaunchSelect& a, uint32_t lp) {
     const char* f = std::getenv("KG_SMALL_PHASES");
     if (!f || !*f || !a.small_replicas || (a.cfg.plugins & 7u) != 7u || a.small_slices * lp <= 512u) return nullptr;
@@ -3344,15 +3383,24 @@ static const char* small_phases_file(const LaunchSelect& a, uint32_t lp) {
 }
 
 static kg_status small_phases_write(kg_ctx* ctx, const char* file, uint32_t nc) {
-    std::vector<uint64_t> h((size_t)nc * 4 + 1);
+    std::vector<uint64_t> h((size_t)nc * 5 + 1);
     h[0] = nc;
-    HIP_TRY(ctx, hipMemcpyAsync(h.data() + 1, ctx->d_phases + 2, sizeof(uint64_t) * nc * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h.data() + 1, ctx->d_phases + 2 * (size_t)nc, sizeof(uint64_t) * nc * 5, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     FILE* fp = std::fopen(file, "ab");
     if (!fp) return fail(ctx, KG_INVALID_ARG, "KG_SMALL_PHASES: cannot open %s", file);
-    const bool ok = std::fwrite(h.data(), sizeof(uint64_t), h.size(), fp) == h.size();
+    bool ok = std::fwrite(h.data(), sizeof(uint64_t), (size_t)nc * 4 + 1, fp) == (size_t)nc * 4 + 1;
     std::fclose(fp);
-    return ok ? KG_OK : fail(ctx, KG_INVALID_ARG, "KG_SMALL_PHASES: short write to %s", file);
+    if (!ok) return fail(ctx, KG_INVALID_ARG, "KG_SMALL_PHASES: short write to %s", file);
+    // the fifth reading keeps the file's record shape: <file>.ops, one record of the workgroup count and one clock
+    // reading per workgroup for every record of <file>
+    const std::string ops = std::string(file) + ".ops";
+    fp = std::fopen(ops.c_str(), "ab");
+    if (!fp) return fail(ctx, KG_INVALID_ARG, "KG_SMALL_PHASES: cannot open %s", ops.c_str());
+    h[(size_t)nc * 4] = nc;  // the last of the four-reading words is written: its place holds the second record's head
+    ok = std::fwrite(h.data() + (size_t)nc * 4, sizeof(uint64_t), (size_t)nc + 1, fp) == (size_t)nc + 1;
+    std::fclose(fp);
+    return ok ? KG_OK : fail(ctx, KG_INVALID_ARG, "KG_SMALL_PHASES: short write to %s", ops.c_str());
 }
 
 static kg_status ensure_sacc(kg_pods* p, uint32_t replicas, uint32_t lp) {
@@ -3507,16 +3555,16 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
             a.pstat = reinterpret_cast<uint32_t*>(p->d_lres + lp);
         }
         // kernel-time bracket (kg_profile_read). One launch: the kernel times itself with the device clock (a.prof: a
-        // slot of the context's table, ensure_prof), the launch is the plain one and the host only counts the slot, once
-        // the launch succeeded. Two launches, a device without a wall clock
+        // region of the context's pool, one pair per workgroup, ensure_prof), the launch is the plain one and the host
+        // only counts the region, once the launch succeeded. Two launches, a device without a wall clock
         // rate, or KG_PROFILE_BOUND_EVENTS (read per call: the tool and the tests compare both brackets): the launch
         // carries a pooled event pair itself (LaunchSelect.ev_start / ev_stop), nothing is recorded on the stream. The
         // pair goes on ev_live only once the launch took it; every failure hands it back to the pool
         const uint32_t nc = a.range[0].n_chunks + a.range[1].n_chunks;
         const char* phases = small_phases_file(a, lp);
         st = KG_OK;
-        if (phases) {  // a launch of the measurement aid has no bracket: its tick pair is the scratch one in d_phases
-            HIP_TRY(ctx, grow(ctx, ctx->d_phases, (size_t)nc * 4 + 2));
+        if (phases) {  // a launch of the measurement aid has no bracket: its pairs are the scratch ones in d_phases
+            HIP_TRY(ctx, grow(ctx, ctx->d_phases, (size_t)nc * 7));
             if (a.small_acc) {  // the ticket that only this instantiation draws: the finisher forms', zero between launches
                 st = ensure_sacc(p, 1, lp);
                 if (st != KG_OK) return st;
@@ -3525,19 +3573,19 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
             a.phases = true;
             a.prof = ctx->d_phases;
         } else if (ctx->profiling && a.small_replicas && !std::getenv("KG_PROFILE_BOUND_EVENTS")) {
-            st = ensure_prof(ctx, &a.prof);
+            st = ensure_prof(ctx, nc, &a.prof);
         }
         if (st == KG_OK && !a.prof) st = bracket_take(ctx, &a.ev_start, &a.ev_stop);
         if (st == KG_OK) {
             const hipError_t le = launch_select(a, ctx->stream);
             if (le != hipSuccess) {
                 bracket_drop(ctx, a.ev_start, a.ev_stop);
-                // the slot is not counted and goes to the next launch: zero, whatever this one wrote
-                if (a.prof && !phases) hipMemsetAsync(a.prof, 0, 2 * sizeof(uint64_t), ctx->stream);
+                // the region is not counted and goes to the next launch: zero, whatever this one wrote
+                if (a.prof && !phases) hipMemsetAsync(a.prof, 0, 2 * sizeof(uint64_t) * nc, ctx->stream);
                 st = fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR, "launch_select(a, ctx->stream): %s",
                           hipGetErrorString(le));
             } else if (a.prof && !phases) {
-                ctx->prof_pending++;
+                prof_take(ctx, nc, a.small_acc);
             } else if (a.ev_start) {
                 ctx->ev_live.emplace_back(a.ev_start, a.ev_stop);
             }
@@ -5073,7 +5121,14 @@ kg_status kg_profile_enable(kg_ctx* ctx, int enable) {
     if (!ctx) return KG_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->mu);
     ctx->profiling = enable != 0;
-    return KG_OK;
+    if (!ctx->profiling) return KG_OK;
+    // the device-clock pool of the one-launch selects: here, not in the first profiled select of a timed loop
+    // (a failure leaves profiling off)
+    ctx->profiling = false;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const kg_status st = prof_pool(ctx);
+    ctx->profiling = st == KG_OK;
+    return st;
 }
 
 kg_status kg_profile_read(kg_ctx* ctx, double* total_ms, uint64_t* launches, int reset) {
@@ -5089,7 +5144,7 @@ kg_status kg_profile_read(kg_ctx* ctx, double* total_ms, uint64_t* launches, int
         ctx->ev_free.push_back(e);
     }
     ctx->ev_live.clear();
-    // the one-launch small selects that timed themselves: their slots since the last drain
+    // the one-launch small selects that timed themselves: their regions since the last drain
     const kg_status dst = prof_drain(ctx);
     if (dst != KG_OK) return dst;
     if (total_ms) *total_ms = ctx->prof_ms;

@@ -47,6 +47,8 @@ def main():
         del os.environ["KG_SMALL_PHASES"]
     raw = np.fromfile(path, dtype=np.uint64)
     os.remove(path)
+    if os.path.exists(path + ".ops"):  # the fifth reading's file (tools/small_prologue.py reads it)
+        os.remove(path + ".ops")
     nc = int(raw[0])
     t = raw.reshape(a.steps, 1 + 4 * nc)[:, 1:].reshape(a.steps, nc, 4).astype(np.int64)
     t0 = t[:, :, 0].min(axis=1)[:, None]

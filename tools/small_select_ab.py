@@ -128,6 +128,8 @@ def main():
             del os.environ["KG_SMALL_PHASES"]
         raw = np.fromfile(path, dtype=np.uint64)
         os.remove(path)
+        if os.path.exists(path + ".ops"):  # the fifth reading's file (tools/small_prologue.py reads it)
+            os.remove(path + ".ops")
         per, at = [], 0
         while at < len(raw):
             nc = int(raw[at])
