@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "kg_layout.h"
+#include "kg_small.h"
 #include "../../include/koordgpu.h"
 
 namespace kg {
@@ -58,27 +59,19 @@ struct LaunchSelect {
     hipEvent_t fork, join;
     // one-pod-block fused top-1 select (k_select_small, k_small_finish): K == 1, fused, every lane a fast lane, at
     // most 256 of them. No memset of out / pstat, no side stream; range[c] holds this path's chunks (at most
-    // SMALL_MAX_CHUNK records each, SMALL_MAX_CHUNKS in all), the F_BIG records are taken inline. small_replicas > 0:
-    // one launch, the workgroups fold into that many replicas of per-lane accumulators and the last to arrive writes
-    // every row; 0: two launches, per-chunk slots merged by k_small_finish
+    // SMALL_MAX_CHUNK records each, SMALL_MAX_CHUNKS in all), the F_BIG records are taken inline. What the launch needs
+    // per form: launch_select_small's checks (kg_kernels.hip)
     bool small;
+    SmallForm small_form;
     uint64_t* skeys;         // [chunks or replicas][lanes rounded up to whole waves] best key per chunk and lane
     uint32_t *sub, *sfhi;    // same shape: highest bound of a KG_ST_UNSUPPORTED pair, high word of the best fast key
-    const uint8_t* lane_of;  // per row of [0, n_rows) the lane whose result it takes
+    const uint8_t* lane_of;  // per row of [0, n_rows) the lane whose result it takes (SLOTS, ROWS, ROWS4)
     uint32_t small_slices;   // waves sets per workgroup, each walking its part of the workgroup's chunk
-    uint32_t small_replicas;  // replicas of the accumulators; they and *sticket are zero before and after every launch
-    uint32_t* sticket;        // arrival counter of the launch
-    bool small_rows4;         // lane_of, out and pstat are 16-byte aligned: the finisher stores four rows per thread and step
-    // lane form of the result (one launch only): out and pstat are tables of one entry per lane (lanes rounded up to
-    // whole waves), the finisher stores each lane's key and status word once and no row; lane_of and n_rows are not
-    // read. The reader expands the rows through its own copy of the row -> lane table
-    bool small_lanes;
-    // the accumulators are the result (one launch only, never together with small_lanes): skeys / sfhi / sub are one
-    // parity of the batch's result accumulators, [small_replicas][lanes rounded up to whole waves] each and contiguous
-    // in that order; no finisher runs and nothing goes back to zero. Instead the launch zeroes acc_zero_n 16-byte words
-    // at acc_zero: what the previous launch left in the other parity. out, pstat, lane_of and n_rows are not read,
-    // sticket only by a phases launch. The reader folds the replicas and applies the status rule
-    bool small_acc;
+    uint32_t small_replicas;  // replicas of the accumulators, 0 exactly for SLOTS. The finisher forms' and *sticket are
+                              // zero before and after every launch
+    uint32_t* sticket;        // arrival counter of the launch (finisher forms; ACC: a phases launch only)
+    // ACC: skeys / sfhi / sub are one parity of the batch's result accumulators, contiguous in that order, and the
+    // launch zeroes acc_zero_n 16-byte words at acc_zero: what the previous launch left in the other parity
     void* acc_zero;  // 16-byte aligned
     uint32_t acc_zero_n;
     // optional timing pair of the small select (both set, or neither): the launch binds ev_start to k_select_small's
@@ -88,14 +81,12 @@ struct LaunchSelect {
     // or (one launch only, never together with the pair) the kernel times itself with the device clock. prof is a
     // region of the launch's own, 16-byte aligned and zero before it: per workgroup c of the grid prof[2 * c] = its
     // entry time and prof[2 * c + 1] = its end time (the finisher's last result store, zero in every other workgroup;
-    // small_acc: the workgroup's last result atomic), plain stores
+    // ACC: the workgroup's last result atomic), plain stores
     uint64_t* prof;
     // measurement aid (KG_SMALL_PHASES): prof is a scratch region of the launch's own, followed by [chunks][4] clock
     // readings per workgroup, see k_select_small
     bool phases;
 };
-constexpr uint32_t SMALL_MAX_CHUNK = 64, SMALL_MAX_CHUNKS = 4096;
-constexpr uint32_t SMALL_WG = 1024;  // most threads of a k_select_small workgroup
 inline uint32_t select_fparts(const LaunchSelect& a) { return a.big_part0 + a.big_y; }
 
 // Block replay (k_rb_top / k_rb_merge / k_rb_fix): window of RB_W pods, RB_K keys kept per pod,

@@ -5,9 +5,11 @@
 //              top-K per lane; per-(chunk, pod) partial keys. Specialised per node storage class
 //              (records are stored grouped by class) and per enabled-plugin set.
 //   k_select_small / k_small_finish  the fused top-1 select of at most 256 fast lanes: both storage classes and
-//              the F_BIG records in one launch that also finishes: the workgroups fold into a few replicas of per-lane
-//              accumulators by atomic maxima and the last to arrive writes every row (no memset, no k_big_sel, no
-//              k_expand_keys). For many rows, or on request: per-chunk slots and k_small_finish as a second launch.
+//              the F_BIG records in one launch (no memset, no k_big_sel, no k_expand_keys): a scan, then one epilogue
+//              per result form (SmallForm). By default the workgroups fold into a few replicas of per-lane accumulators
+//              by atomic maxima and the launch ends at its last workgroup: the reader folds the replicas. On request
+//              the last workgroup to arrive finishes (lanes or rows); for many rows: per-chunk slots and
+//              k_small_finish as a second launch.
 //   k_big_sel  the nodes outside the float64 fast path (F_BIG records) for the fast lanes, on the
 //              integer path, chunked over the device's F_BIG list.
 //   k_merge    per pod: top-K over partial keys (global selectHost of one shard or of the
@@ -267,89 +269,68 @@ __global__ __launch_bounds__(256) KG_SEL1_ATTR void k_select1(const NodeRec* __r
     if (live && top) atomicMax((unsigned long long*)(out + o), (unsigned long long)top);
 }
 
-// One-pod-block fused top-1 select (LaunchSelect.small): both storage classes and the F_BIG records in one launch,
-// and nothing to zero in a steady-state step. acc_r > 0: the launch finishes itself (the epilogue below: replicated
-// accumulators, a ticket, the last workgroup writes out / pstat of every row); acc_r == 0: the slot form
-// described here, no atomics, k_small_finish follows. grid (1, nc1 + nc0): workgroups [0, nc1) take class-1 chunks of chunk1 records (the
-// zone walk makes them the dearer ones: they start first), the others class-0 chunks of chunk0; at most 64 records
-// per chunk. A block is `slices` copies of the fast lanes rounded up to whole waves (lp): slice s walks the s-th part
-// of the chunk, so a compute unit holds several waves per SIMD that hide each other's record loads (one wave per SIMD
-// spends three quarters of its time waiting for them); the slices' results meet in LDS. Slice 0 stores
-// every lane's best key of the chunk and its status pair (below) into slot [chunk][lane] of skeys / sub / sfhi (idle
-// lanes: zeros): every slot is written by every launch, and k_small_finish merges them. The fast records go through
-// select1_loop (the arithmetic of k_select1); the F_BIG records of the slice's part (flagged on the record, so the
-// branch is wave-uniform; the device's F_BIG list is not read) follow on the integer path, with k_big_sel's
-// NodeResourcesFit / LoadAware bound prune against the lane's best key so far: a floor below the pod's final key, so no
-// record that could win is skipped. Keys hold the inverted node index: the maximum does not depend on the order of
-// evaluation. The slice index is read from the wave's first lane, so that the compiler sees the record range as
-// wave-uniform and select1_loop keeps its wide scalar record loads. WG: the launch bound, 512 (up to 256 VGPRs: the
-// inline integer path fits without scratch) or 1024 (128 VGPRs: it spills; more copies per workgroup). The chunks are
-// dealt to the XCDs in contiguous runs (xcd_block; launch order measured the same).
-// prof (nullable; only with acc_r > 0): the launch times itself for kg_profile_read with the device-wide 100 MHz clock
+// One-pod-block fused top-1 select (LaunchSelect.small; DESIGN.md §4 holds the measurements): both storage classes and
+// the F_BIG records in one launch, nothing to zero in a steady-state step. k_select_small is a scan, after which slice 0
+// holds every lane's {top, fhi, ub} over the workgroup's chunk, and one epilogue per result form (SmallForm,
+// kg_small.h); each piece is described where it stands. grid (1, nc1 + nc0): workgroups [0, nc1) take class-1 chunks of
+// chunk1 records (the dearer ones start first), the others class-0 chunks of chunk0; at most 64 records per chunk. A
+// block is `slices` copies of the fast lanes rounded up to whole waves (lp): slice s walks the s-th part of the chunk,
+// so that several waves per SIMD hide each other's record loads. WG: the launch bound, 512 (up to 256 VGPRs: the inline
+// integer path fits without scratch) or 1024 (128 VGPRs: it spills; more copies). The chunks go to the XCDs in
+// contiguous runs (xcd_block).
+// prof (nullable; one-launch forms only): the launch times itself for kg_profile_read with the device-wide clock
 // (wall_clock64), so that the dispatch carries no event pair. prof is the launch's own region of the context's pool,
-// zero when the launch starts: one 16-byte pair {entry time, end time} per workgroup, [2 * c] and [2 * c + 1], written
-// by plain stores of its own workgroup only: no two workgroups meet on an address, nothing serialises at the end of
-// the launch. Thread 0 keeps its entry time in LDS (prof_t0). The end: the finisher, once its result stores (rows or
-// lanes) have completed, stores its pair; every other workgroup of a finisher form stores its entry word alone and
-// leaves the end word zero. Without a finisher (SMALL_FORM_ACC) the slice-0 wave that counts itself last in acc_done,
-// behind the completion of every result atomic of the workgroup, stores the pair. The host folds the pairs (earliest
-// entry, latest end) and re-zeroes the region. With prof == nullptr the kernel runs two uniform branches more and
-// nothing else.
-// PH (KG_SMALL_PHASES, a measurement aid; off in every instantiation the library launches by default): prof is set and
-// a scratch region of the launch's own, followed by four clock readings per workgroup that thread 0 stores: entry, loops done
-// (after the slices met in LDS), ticket drawn (SMALL_FORM_ACC: result atomics complete) and, the finisher only
-// (SMALL_FORM_ACC: the workgroup that draws PH's last ticket; else zero), results stored. Behind the [chunks][4]
-// readings follows one more per workgroup, "pod operands ready": thread 0's clock once its lane's PodF is converted.
-// form (uniform; acc_r > 0 only): what the finisher stores. SMALL_FORM_ROWS / SMALL_FORM_ROWS4: out / pstat of every
-// row through lane_of, one by one or four at a time (below). SMALL_FORM_LANES: out and pstat are per-lane tables of lp
-// entries and slice 0's thread j < n_lanes stores its lane's key and status word to out[j] / pstat[j]; lane_of and
-// n_rows are not read, the launch's cost does not depend on the row count, and whoever reads the result expands it
-// (kg_result_keys on the host, through the same row -> lane table). One workgroup alone on the chip storing
-// n_rows x 12 bytes was 2 of the finisher's 3.3 us at config 2's 10,000 rows. SMALL_FORM_ACC: no
-// finisher at all; skeys / sfhi / sub are one parity of the batch's result accumulators and stay as the launch leaves
-// them, the reader folds the replicas and applies the status rule (fold_acc, kg_runtime.cpp); zero / zero_n are the
-// other parity's dirty 16-byte words (0 in every other form), out, pstat, lane_of and n_rows are not read, and ticket
-// only by PH.
-constexpr uint32_t SMALL_FORM_ROWS = 0, SMALL_FORM_ROWS4 = 1, SMALL_FORM_LANES = 2, SMALL_FORM_ACC = 3;
+// zero when the launch starts: one 16-byte pair {entry time, end time} per workgroup, written by plain stores of its own
+// workgroup only. Thread 0 keeps its entry time in LDS; each epilogue says where its bracket ends. With prof == nullptr
+// the kernel runs two uniform branches more and nothing else.
+// PH (KG_SMALL_PHASES, a measurement aid; off in every instantiation the library launches by default): prof is a scratch
+// region, followed by four clock readings per workgroup that thread 0 stores (entry, loops done, two that the epilogue
+// names) and, behind those, one more each: "pod operands ready".
 constexpr uint32_t SMALL_ROW_STEPS = 4;  // the finisher's lane words in flight per thread
-template <uint32_t PM, uint32_t WG, bool PH = false>
-__global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__ nodes, const ZoneRec* __restrict__ zones,
-                                                           PodsDev pods, uint32_t n_lanes, uint32_t lp, uint32_t n0,
-                                                           uint32_t n_end, uint32_t chunk0, uint32_t chunk1, uint32_t nc1,
-                                                           uint32_t index_base, KCfg cfg, uint64_t* __restrict__ skeys,
-                                                           uint32_t* __restrict__ sub, uint32_t* __restrict__ sfhi,
-                                                           const uint32_t* __restrict__ order, uint32_t acc_r,
-                                                           uint32_t* __restrict__ ticket,
-                                                           const uint8_t* __restrict__ lane_of, uint32_t n_rows,
-                                                           uint64_t* __restrict__ out, uint32_t* __restrict__ pstat,
-                                                           uint64_t* __restrict__ prof, uint32_t form,
-                                                           uint4* __restrict__ zero, uint32_t zero_n) {
-    __shared__ uint64_t lk[WG];
-    __shared__ uint2 ls[WG];
-    __shared__ uint32_t acc_done;  // prof in SMALL_FORM_ACC: slice-0 waves whose result atomics have completed
-    uint64_t ph_entry = 0, ph_loops = 0, ph_ops = 0;
-    __shared__ uint64_t prof_t0;   // prof: the workgroup's entry time
-    uint64_t* const phases = prof + 2 * (size_t)gridDim.y;  // PH only
-    if (PH || prof) {  // uniform
-        const uint64_t t_in = wall_clock64();
-        if (PH) ph_entry = t_in;
-        if (prof && threadIdx.x == 0) {
-            acc_done = 0u;
-            prof_t0 = t_in;
+
+// A thread's place: workgroup c, lane j of slice sl (live: below n_lanes), and the workgroup's LDS, a key and a {fhi, ub}
+// pair per thread. sl is read from the wave's first lane (lp is whole waves), so that the compiler sees the record
+// range as wave-uniform and select1_loop keeps its wide scalar record loads.
+struct SmallWg {
+    uint32_t c, slices, lp, j, sl;
+    bool live;
+    uint64_t* lk;
+    uint2* ls;
+};
+struct SmallClock {  // prof, the PH readings behind it, the workgroup's entry time and end counter in LDS
+    uint64_t *prof, *phases, *t0;
+    uint32_t* done;
+    uint64_t ph_entry, ph_ops;
+};
+
+// The slices' values meet in LDS: afterwards slice 0 holds each lane's maxima over all slices.
+__device__ __forceinline__ void small_merge_slices(const SmallWg& w, uint64_t& top, uint2& st) {
+    w.lk[threadIdx.x] = top;
+    w.ls[threadIdx.x] = st;
+    __syncthreads();
+    if (w.sl == 0) {
+        for (uint32_t s2 = 1; s2 < w.slices; s2++) {
+            const uint64_t k2 = w.lk[s2 * w.lp + w.j];
+            const uint2 t2 = w.ls[s2 * w.lp + w.j];
+            st.x = max(st.x, t2.x);
+            st.y = max(st.y, t2.y);
+            top = k2 > top ? k2 : top;
         }
     }
-    const uint32_t c = xcd_block().y, slices = blockDim.x / lp;
-    // SMALL_FORM_ACC: what the previous launch on the batch left in the other parity's accumulators goes back to zero.
-    // Whole 128-byte lines: line c + k * chunks to workgroup c, eight neighbouring lanes a 16-byte word each, so that
-    // no line is written from two workgroups (two XCDs' L2s); nothing waits on the stores
-    for (uint32_t i = (c + (threadIdx.x >> 3) * gridDim.y) * 8u + (threadIdx.x & 7u); i < zero_n;
-         i += (blockDim.x >> 3) * gridDim.y * 8u) {
-        zero[i] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    const uint32_t j = threadIdx.x % lp;
-    const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / lp));  // lp is whole waves
-    const bool live = j < n_lanes;
-    const uint32_t row = live ? (order ? order[j] : j) : 0u;
+}
+
+// The scan. The fast records of the slice's part go through select1_loop (the arithmetic of k_select1); its F_BIG
+// records (flagged on the record, so the branch is wave-uniform) follow on the integer path, with k_big_sel's bound prune
+// against the lane's best key so far: a floor below the pod's final key, so no record that could win is skipped. Keys
+// hold the inverted node index: the maximum does not depend on the order of evaluation. Then the slices merge.
+template <uint32_t PM, bool PH>
+__device__ __forceinline__ void small_scan(const NodeRec* nodes, const ZoneRec* zones, const PodsDev& pods,
+                                           const uint32_t* order, uint32_t n0, uint32_t n_end, uint32_t chunk0,
+                                           uint32_t chunk1, uint32_t nc1, uint32_t index_base, const KCfg& cfg,
+                                           const SmallWg& w, uint64_t& top, uint2& st, uint64_t& ph_ops) {
+    const uint32_t c = w.c, sl = w.sl;
+    const bool live = w.live;
+    const uint32_t row = live ? (order ? order[w.j] : w.j) : 0u;
     const PodV p = load_pod(pods, row);
     const bool cls1 = c < nc1;  // uniform
     const uint32_t wlo = cls1 ? n0 + c * chunk1 : (c - nc1) * chunk0;
@@ -367,9 +348,8 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
     }
     const KCfg cv = cfg_in_vgprs(cfg);
     const bool prod = __all(!live || fast_kind_match(FK_PROD, p)), batch = __all(!live || fast_kind_match(FK_BATCH, p));
-    const uint32_t span = (whi - wlo + slices - 1) / slices;
+    const uint32_t span = (whi - wlo + w.slices - 1) / w.slices;
     const uint32_t lo = min(whi, wlo + sl * span), hi = min(whi, lo + span);
-    uint64_t top;
     if (!cls1) {
         if (prod) top = select1_loop<PM, 0, FK_PROD>(nodes, zones, lo, hi, index_base, cv, pf);
         else if (batch) top = select1_loop<PM, 0, FK_BATCH>(nodes, zones, lo, hi, index_base, cv, pf);
@@ -385,8 +365,8 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
     // status as k_big_sel would set it behind the fast records' kernels: there a pair is evaluated (and its
     // KG_ST_UNSUPPORTED seen) when its bound reaches the pod's best key over ALL fast records. The prune here uses the
     // best fast key of this part only (lower: a superset is evaluated), and keeps what the finish needs to decide as
-    // k_big_sel does: the high word of that fast key and, over the pairs found KG_ST_UNSUPPORTED, the highest bound
-    // (high word + 1; 0xFFFFFFFF for an F_VBIG record, which is never pruned)
+    // k_big_sel does (small_status): the high word of that fast key and, over the pairs found KG_ST_UNSUPPORTED, the
+    // highest bound (high word + 1; 0xFFFFFFFF for an F_VBIG record, which is never pruned)
     const uint32_t fhi = (uint32_t)(top >> 32);
     const uint64_t floor_key = top;
     uint32_t ub = 0;
@@ -412,102 +392,138 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
             top = key > top ? key : top;
         }
     }
-    uint2 st = make_uint2(fhi, ub);
-    if (slices > 1) {  // uniform
-        lk[threadIdx.x] = top;
-        ls[threadIdx.x] = st;
-        __syncthreads();
-        if (sl == 0) {
-            for (uint32_t s2 = 1; s2 < slices; s2++) {
-                const uint64_t k2 = lk[s2 * lp + j];
-                const uint2 t2 = ls[s2 * lp + j];
-                st.x = max(st.x, t2.x);
-                st.y = max(st.y, t2.y);
-                top = k2 > top ? k2 : top;
-            }
-        }
-    }
-    if (acc_r == 0) {  // uniform: the slot tables, k_small_finish follows
-        if (sl != 0) return;
-        const size_t slot = (size_t)c * lp + j;
-        skeys[slot] = live ? top : 0ull;
-        sfhi[slot] = live ? st.x : 0u;
-        sub[slot] = live ? st.y : 0u;
-        return;
-    }
-    // SMALL_FORM_ACC: the accumulators are the result. Slice 0 folds into replica c % acc_r as the finisher forms do
-    // (below), into the parity that the launch before zeroed, and the workgroup is done: no ticket, no barrier, no
-    // acquire, nothing read back. The other slices' waves have left after the LDS barrier. With prof every slice-0 wave
-    // waits for its own atomics and counts itself in LDS (acc_done, no wave waits for another); the wave that counts
-    // last reads the clock, behind the completion of every result atomic of the workgroup, and stores the workgroup's
-    // pair: one plain 16-byte store per workgroup to a word of its own. (End atomics on one shared word arrive together
-    // and the launch cannot end before them: one per wave, 753 at config 2, cost 6 us, one per workgroup 2; DESIGN.md
-    // §4.) PH keeps the shape of its record: reading 3 is
-    // "result atomics complete" (the workgroup's, behind a barrier), and a relaxed returned ticket, which only this
-    // instantiation draws, lets the last workgroup store reading 4 and take the ticket back to zero.
-    if (form == SMALL_FORM_ACC) {  // uniform
-        if (PH) ph_loops = wall_clock64();
-        if (!PH && sl != 0) return;
-        if (prof && slices == 1) __syncthreads();  // uniform: acc_done is zero, prof_t0 set (else the LDS barrier above)
-        if (sl == 0 && live) {
-            const size_t at = (size_t)(c % acc_r) * lp + j;
-            __hip_atomic_fetch_max(skeys + at, top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_max(sfhi + at, st.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (st.y) __hip_atomic_fetch_max(sub + at, st.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (PH || prof) {  // uniform
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            // the slice-0 wave that counts itself last reads the clock behind every other's completion
-            if (prof && sl == 0 && (threadIdx.x & 63u) == 0u && atomicAdd(&acc_done, 1u) == lp / 64u - 1u)
-                *reinterpret_cast<ulonglong2*>(prof + 2 * (size_t)c) = make_ulonglong2(prof_t0, wall_clock64());
-        }
-        if (PH) {
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                uint64_t* slot = phases + (size_t)c * 4;
-                slot[0] = ph_entry;
-                slot[1] = ph_loops;
-                slot[2] = wall_clock64();
-                const bool last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.y - 1u;
-                if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                slot[3] = last ? wall_clock64() : 0ull;
-                phases[4 * (size_t)gridDim.y + c] = ph_ops;
-            }
-        }
-        return;
-    }
-    // One launch: fold into replica c % acc_r of the per-lane accumulators (skeys / sfhi / sub are then [acc_r][lp],
-    // all zero between launches) by no-return agent-scope atomic maxima, each array lane-contiguous so that a wave's
-    // instruction covers 512 / 256 contiguous bytes; idle lanes add nothing, sub only what is set. Then the arrival
-    // hand-off in its counter form: every wave drains its atomics, workgroup barrier, one returned add on the ticket;
-    // no workgroup waits for another, whatever the residency. The workgroup that draws the last ticket finishes.
-    if (PH) ph_loops = wall_clock64();
-    if (sl == 0 && live) {
-        const size_t at = (size_t)(c % acc_r) * lp + j;
+    st = make_uint2(fhi, ub);
+    if (w.slices > 1) small_merge_slices(w, top, st);  // uniform
+}
+
+// SLOTS: no atomics, k_small_finish follows. Slice 0 stores every lane's best key of the chunk and its status pair into
+// slot [chunk][lane] of skeys / sfhi / sub (idle lanes: zeros): every slot is written by every launch.
+__device__ __forceinline__ void small_store_slots(const SmallWg& w, uint64_t* skeys, uint32_t* sfhi, uint32_t* sub,
+                                                  uint64_t top, uint2 st) {
+    if (w.sl != 0) return;
+    const size_t slot = (size_t)w.c * w.lp + w.j;
+    skeys[slot] = w.live ? top : 0ull;
+    sfhi[slot] = w.live ? st.x : 0u;
+    sub[slot] = w.live ? st.y : 0u;
+}
+
+// The one-launch forms: slice 0 folds into replica c % acc_r of the per-lane accumulators (skeys / sfhi / sub are then
+// [acc_r][lp]) by no-return agent-scope atomic maxima, each array lane-contiguous so that a wave's instruction covers
+// 512 / 256 contiguous bytes; idle lanes add nothing, sub only what is set.
+__device__ __forceinline__ void small_acc_max(const SmallWg& w, uint32_t acc_r, uint64_t* skeys, uint32_t* sfhi,
+                                              uint32_t* sub, uint64_t top, uint2 st) {
+    if (w.sl == 0 && w.live) {
+        const size_t at = (size_t)(w.c % acc_r) * w.lp + w.j;
         __hip_atomic_fetch_max(skeys + at, top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_fetch_max(sfhi + at, st.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (st.y) __hip_atomic_fetch_max(sub + at, st.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+// ACC: the accumulators are the result. skeys / sfhi / sub are the parity that the launch before zeroed and stay as the
+// maxima leave them: no ticket, no barrier, no acquire, nothing read back; the reader folds the replicas (fold_acc,
+// kg_small.h). The other slices' waves have left after the LDS barrier. With prof every slice-0 wave waits for its own
+// atomics and counts itself in LDS (t.done); the wave that counts last reads the clock and stores the workgroup's pair:
+// one plain 16-byte store per workgroup to a word of its own (end atomics on a shared word cost 2 to 6 us, DESIGN.md
+// §4). PH: reading 3 is "result atomics complete" (behind a barrier), and a relaxed returned ticket, which only this
+// instantiation draws, lets the last workgroup store reading 4 (else zero) and take the ticket back to zero.
+template <bool PH>
+__device__ __forceinline__ void small_end_acc(const SmallWg& w, const SmallClock& t, uint32_t acc_r, uint64_t* skeys,
+                                              uint32_t* sfhi, uint32_t* sub, uint32_t* ticket, uint64_t top, uint2 st) {
+    uint64_t ph_loops = 0;
+    if (PH) ph_loops = wall_clock64();
+    if (!PH && w.sl != 0) return;
+    if (t.prof && w.slices == 1) __syncthreads();  // uniform: *t.done is zero, *t.t0 set (else the scan's LDS barrier)
+    small_acc_max(w, acc_r, skeys, sfhi, sub, top, st);
+    if (PH || t.prof) {  // uniform
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // the slice-0 wave that counts itself last reads the clock behind every other's completion
+        if (t.prof && w.sl == 0 && (threadIdx.x & 63u) == 0u && atomicAdd(t.done, 1u) == w.lp / 64u - 1u)
+            *reinterpret_cast<ulonglong2*>(t.prof + 2 * (size_t)w.c) = make_ulonglong2(*t.t0, wall_clock64());
+    }
+    if (PH) {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint64_t* slot = t.phases + (size_t)w.c * 4;
+            slot[0] = t.ph_entry;
+            slot[1] = ph_loops;
+            slot[2] = wall_clock64();
+            const bool last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.y - 1u;
+            if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            slot[3] = last ? wall_clock64() : 0ull;
+            t.phases[4 * (size_t)gridDim.y + w.c] = t.ph_ops;
+        }
+    }
+}
+
+// The finisher's row stores (ROWS, ROWS4): every row takes its lane's key and status word from LDS. rows4 (uniform): four
+// rows per thread and step, one 32-bit word of lane_of, then 2 x 16 bytes of keys and 16 bytes of status. A thread issues
+// the lane words of SMALL_ROW_STEPS steps before its first store, so up to 16 rows x the workgroup's threads cost one
+// load round trip. The rows past the last multiple of four, or all of them, go one by one.
+__device__ __forceinline__ void small_store_rows(const SmallWg& w, bool rows4, const uint8_t* lane_of, uint32_t n_rows,
+                                                 uint64_t* out, uint32_t* pstat) {
+    const uint32_t n4 = rows4 ? n_rows / 4u : 0u;
+    const uint32_t* const lane4 = reinterpret_cast<const uint32_t*>(lane_of);
+    for (uint32_t q0 = threadIdx.x; q0 < n4; q0 += SMALL_ROW_STEPS * blockDim.x) {
+        uint32_t v[SMALL_ROW_STEPS];
+#pragma unroll
+        for (uint32_t u = 0; u < SMALL_ROW_STEPS; u++) {
+            const uint32_t q = q0 + u * blockDim.x;
+            v[u] = q < n4 ? lane4[q] : 0u;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < SMALL_ROW_STEPS; u++) {
+            const uint32_t q = q0 + u * blockDim.x;
+            if (q < n4) {
+                const uint32_t l0 = v[u] & 255u, l1 = (v[u] >> 8) & 255u, l2 = (v[u] >> 16) & 255u, l3 = v[u] >> 24;
+                ulonglong2* const o = reinterpret_cast<ulonglong2*>(out + 4u * (size_t)q);
+                o[0] = make_ulonglong2(w.lk[l0], w.lk[l1]);
+                o[1] = make_ulonglong2(w.lk[l2], w.lk[l3]);
+                *reinterpret_cast<uint4*>(pstat + 4u * (size_t)q) =
+                    make_uint4(w.ls[l0].x, w.ls[l1].x, w.ls[l2].x, w.ls[l3].x);
+            }
+        }
+    }
+    for (uint32_t r = 4u * n4 + threadIdx.x; r < n_rows; r += blockDim.x) {
+        const uint32_t l = lane_of[r];
+        out[r] = w.lk[l];
+        pstat[r] = w.ls[l].x;
+    }
+}
+
+// ROWS, ROWS4, LANES: the launch finishes itself. The maxima go into accumulators that are all zero between launches;
+// then the arrival hand-off in its counter form: every wave drains its atomics, workgroup barrier, one returned add on
+// the ticket; no workgroup waits for another. The workgroup that draws the last ticket is the finisher: one agent-scope
+// acquire, then every accumulator word is read and reset in one returned agent-scope exchange, folded over the replicas
+// per lane through LDS, and the ticket goes back to zero too. LANES: slice 0's thread j < n_lanes stores its lane's key
+// and status word to out[j] / pstat[j]; lane_of and n_rows are not read and the reader expands the rows. Else the rows
+// (small_store_rows). prof: the finisher, once its result stores have completed, stores its pair; every other workgroup
+// stores its entry word alone. PH: reading 3 is "ticket drawn", reading 4 the finisher's "results stored" (else zero).
+template <bool PH>
+__device__ __forceinline__ void small_end_finisher(const SmallWg& w, const SmallClock& t, SmallForm form, uint32_t acc_r,
+                                                   uint64_t* skeys, uint32_t* sfhi, uint32_t* sub, uint32_t* ticket,
+                                                   const uint8_t* lane_of, uint32_t n_rows, uint64_t* out,
+                                                   uint32_t* pstat, uint64_t top, uint2 st) {
+    uint64_t ph_loops = 0;
+    if (PH) ph_loops = wall_clock64();
+    small_acc_max(w, acc_r, skeys, sfhi, sub, top, st);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // also: slice 0 has read every other slice's lk / ls
     if (threadIdx.x == 0)
-        lk[0] = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.y - 1u;
+        w.lk[0] = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.y - 1u;
     __syncthreads();
     if (PH && threadIdx.x == 0) {
-        uint64_t* slot = phases + (size_t)c * 4;
-        slot[0] = ph_entry;
+        uint64_t* slot = t.phases + (size_t)w.c * 4;
+        slot[0] = t.ph_entry;
         slot[1] = ph_loops;
         slot[2] = wall_clock64();
         slot[3] = 0;
-        phases[4 * (size_t)gridDim.y + c] = ph_ops;
+        t.phases[4 * (size_t)gridDim.y + w.c] = t.ph_ops;
     }
-    if (lk[0] == 0ull) {  // uniform
-        if (prof && threadIdx.x == 0) prof[2 * (size_t)c] = prof_t0;
+    if (w.lk[0] == 0ull) {  // uniform
+        if (t.prof && threadIdx.x == 0) t.prof[2 * (size_t)w.c] = *t.t0;
         return;
     }
-    // The finisher: one agent-scope acquire for the workgroup, then every accumulator word is read and reset in one
-    // returned agent-scope exchange (atomics both sides of the hand-off), folded over the replicas per lane through
-    // LDS, and every row takes its lane's result as k_small_finish writes it. The ticket goes back to zero too.
     if (threadIdx.x == 0) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -516,10 +532,10 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
     __syncthreads();  // also: every thread has read the verdict in lk[0]
     top = 0;
     st = make_uint2(0u, 0u);
-    if (live) {
+    if (w.live) {
 #pragma unroll 4
-        for (uint32_t r = sl; r < acc_r; r += slices) {
-            const size_t at = (size_t)r * lp + j;
+        for (uint32_t r = w.sl; r < acc_r; r += w.slices) {
+            const size_t at = (size_t)r * w.lp + w.j;
             const uint64_t k2 = __hip_atomic_exchange(skeys + at, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const uint32_t f2 = __hip_atomic_exchange(sfhi + at, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const uint32_t u2 = __hip_atomic_exchange(sub + at, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -528,71 +544,75 @@ __global__ __launch_bounds__(WG) void k_select_small(const NodeRec* __restrict__
             st.y = max(st.y, u2);
         }
     }
-    lk[threadIdx.x] = top;
-    ls[threadIdx.x] = st;
-    __syncthreads();
-    if (sl == 0) {
-        for (uint32_t s2 = 1; s2 < slices; s2++) {
-            const uint64_t k2 = lk[s2 * lp + j];
-            const uint2 t2 = ls[s2 * lp + j];
-            st.x = max(st.x, t2.x);
-            st.y = max(st.y, t2.y);
-            top = k2 > top ? k2 : top;
-        }
-        // bit 0 of the status word: KG_ST_UNSUPPORTED when an unsupported pair's bound reaches the best fast key
-        st.x = st.y != 0u && st.y > st.x ? KG_ST_UNSUPPORTED : 0u;
-        if (form == SMALL_FORM_LANES) {  // uniform: one key and one status word per lane, whatever the row count
-            if (live) {
-                out[j] = top;
-                pstat[j] = st.x;
+    small_merge_slices(w, top, st);
+    if (w.sl == 0) {
+        st.x = small_status(st.x, st.y);
+        if (form == SMALL_LANES) {  // uniform: one key and one status word per lane, whatever the row count
+            if (w.live) {
+                out[w.j] = top;
+                pstat[w.j] = st.x;
             }
         } else {
-            ls[j] = make_uint2(st.x, 0u);
-            lk[j] = top;
+            w.ls[w.j] = make_uint2(st.x, 0u);
+            w.lk[w.j] = top;
         }
     }
     __syncthreads();
-    // Four rows per thread and step: one 32-bit word of lane_of, then 2 x 16 bytes of keys and 16 bytes of status
-    // (rows4, uniform: lane_of, out and pstat are 16-byte aligned, the host checks it; else every row goes through
-    // the loop below). A thread issues the lane words of SMALL_ROW_STEPS steps before its first store, so up to 16
-    // rows x the workgroup's threads cost one load round trip; a one-byte load and two stores per thread and 1,024
-    // rows made ten load-then-store round trips of 10,000 rows (the stores count on the loads' counter). The rows
-    // past the last multiple of four go one by one. The lane form has no rows to store.
-    if (form == SMALL_FORM_LANES) n_rows = 0u;
-    const uint32_t n4 = form == SMALL_FORM_ROWS4 ? n_rows / 4u : 0u;
-    const uint32_t* const lane4 = reinterpret_cast<const uint32_t*>(lane_of);
-    for (uint32_t q0 = threadIdx.x; q0 < n4; q0 += SMALL_ROW_STEPS * blockDim.x) {
-        uint32_t w[SMALL_ROW_STEPS];
-#pragma unroll
-        for (uint32_t u = 0; u < SMALL_ROW_STEPS; u++) {
-            const uint32_t q = q0 + u * blockDim.x;
-            w[u] = q < n4 ? lane4[q] : 0u;
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < SMALL_ROW_STEPS; u++) {
-            const uint32_t q = q0 + u * blockDim.x;
-            if (q < n4) {
-                const uint32_t l0 = w[u] & 255u, l1 = (w[u] >> 8) & 255u, l2 = (w[u] >> 16) & 255u, l3 = w[u] >> 24;
-                ulonglong2* const o = reinterpret_cast<ulonglong2*>(out + 4u * (size_t)q);
-                o[0] = make_ulonglong2(lk[l0], lk[l1]);
-                o[1] = make_ulonglong2(lk[l2], lk[l3]);
-                *reinterpret_cast<uint4*>(pstat + 4u * (size_t)q) = make_uint4(ls[l0].x, ls[l1].x, ls[l2].x, ls[l3].x);
-            }
-        }
-    }
-    for (uint32_t r = 4u * n4 + threadIdx.x; r < n_rows; r += blockDim.x) {
-        const uint32_t l = lane_of[r];
-        out[r] = lk[l];
-        pstat[r] = ls[l].x;
-    }
-    if (PH || prof) {  // uniform: the bracket ends when every result store of the workgroup has completed
+    small_store_rows(w, form == SMALL_ROWS4, lane_of, form == SMALL_LANES ? 0u : n_rows, out, pstat);
+    if (PH || t.prof) {  // uniform: the bracket ends when every result store of the workgroup has completed
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (threadIdx.x == 0) {
             const uint64_t t_end = wall_clock64();
-            if (PH) phases[(size_t)c * 4 + 3] = t_end;
-            if (prof) *reinterpret_cast<ulonglong2*>(prof + 2 * (size_t)c) = make_ulonglong2(prof_t0, t_end);
+            if (PH) t.phases[(size_t)w.c * 4 + 3] = t_end;
+            if (t.prof) *reinterpret_cast<ulonglong2*>(t.prof + 2 * (size_t)w.c) = make_ulonglong2(*t.t0, t_end);
         }
+    }
+}
+
+template <uint32_t PM, uint32_t WG, bool PH = false>
+__global__ __launch_bounds__(WG) void k_select_small(
+    const NodeRec* __restrict__ nodes, const ZoneRec* __restrict__ zones, PodsDev pods, uint32_t n_lanes, uint32_t lp,
+    uint32_t n0, uint32_t n_end, uint32_t chunk0, uint32_t chunk1, uint32_t nc1, uint32_t index_base, KCfg cfg,
+    uint64_t* __restrict__ skeys, uint32_t* __restrict__ sub, uint32_t* __restrict__ sfhi, const uint32_t* __restrict__ order,
+    uint32_t acc_r, uint32_t* __restrict__ ticket, const uint8_t* __restrict__ lane_of, uint32_t n_rows,
+    uint64_t* __restrict__ out, uint32_t* __restrict__ pstat, uint64_t* __restrict__ prof, SmallForm form,
+    uint4* __restrict__ zero, uint32_t zero_n) {
+    __shared__ uint64_t lk[WG];
+    __shared__ uint2 ls[WG];
+    __shared__ uint32_t acc_done;  // prof in ACC: slice-0 waves whose result atomics have completed
+    __shared__ uint64_t prof_t0;   // prof: the workgroup's entry time
+    SmallClock t{prof, prof + 2 * (size_t)gridDim.y, &prof_t0, &acc_done, 0, 0};
+    if (PH || prof) {  // uniform
+        const uint64_t t_in = wall_clock64();
+        if (PH) t.ph_entry = t_in;
+        if (prof && threadIdx.x == 0) {
+            acc_done = 0u;
+            prof_t0 = t_in;
+        }
+    }
+    const uint32_t c = xcd_block().y, slices = blockDim.x / lp;
+    // ACC (zero_n is 0 in every other form): what the previous launch on the batch left in the other parity's
+    // accumulators goes back to zero. Whole 128-byte lines: line c + k * chunks to workgroup c, eight neighbouring lanes a
+    // 16-byte word each, so that no line is written from two workgroups (two XCDs' L2s); nothing waits on the stores
+    for (uint32_t i = (c + (threadIdx.x >> 3) * gridDim.y) * 8u + (threadIdx.x & 7u); i < zero_n;
+         i += (blockDim.x >> 3) * gridDim.y * 8u) {
+        zero[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    const uint32_t j = threadIdx.x % lp;
+    const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / lp));
+    const SmallWg w{c, slices, lp, j, sl, j < n_lanes, lk, ls};
+    uint64_t top;
+    uint2 st;
+    small_scan<PM, PH>(nodes, zones, pods, order, n0, n_end, chunk0, chunk1, nc1, index_base, cfg, w, top, st, t.ph_ops);
+    // The epilogue of the form (uniform). SMALL_SLOTS is told by its replica count, 0 exactly for it, so that the other
+    // epilogues are compiled with acc_r != 0 known: a switch on the form alone moved the 1,024-thread variants' spills.
+    if (acc_r == 0) {
+        small_store_slots(w, skeys, sfhi, sub, top, st);
+    } else if (form == SMALL_ACC) {
+        small_end_acc<PH>(w, t, acc_r, skeys, sfhi, sub, ticket, top, st);
+    } else {
+        small_end_finisher<PH>(w, t, form, acc_r, skeys, sfhi, sub, ticket, lane_of, n_rows, out, pstat, top, st);
     }
 }
 
@@ -678,7 +698,7 @@ __global__ __launch_bounds__(SMALL_FIN_WG) void k_small_finish(const uint64_t* _
     if (r < n) {
         const uint32_t l = lane_of[r];
         out[r] = mk[l];
-        pstat[r] = mu[l] != 0u && mu[l] > mf[l] ? KG_ST_UNSUPPORTED : 0u;
+        pstat[r] = small_status(mf[l], mu[l]);
     }
 }
 
@@ -1509,7 +1529,27 @@ static void select_fast(const LaunchSelect& a, const SelectRange& r, hipStream_t
     }
 }
 
-// LaunchSelect.small: k_select_small over both classes' chunks, finishing inside the launch (small_replicas > 0) or
+// What each form of the one-pod-block select needs of LaunchSelect, and what it must not carry.
+static bool small_args_ok(const LaunchSelect& a) {
+    if (!a.skeys || !a.sub || !a.sfhi) return false;
+    if (a.prof && (a.ev_start || a.ev_stop)) return false;  // the device clock or the bound pair, never both
+    if (a.phases && !a.prof) return false;
+    const bool tables = a.out && a.pstat && !a.acc_zero_n;  // a result to store, no other parity to zero
+    switch (a.small_form) {
+        case SMALL_SLOTS:  // two launches: the row -> lane table for k_small_finish; the kernel cannot time the step
+            return a.small_replicas == 0 && tables && a.lane_of && !a.prof;
+        case SMALL_ROWS:
+        case SMALL_ROWS4:  // the finisher stores rows through lane_of
+            return a.small_replicas != 0 && tables && a.lane_of && a.sticket;
+        case SMALL_LANES:  // out / pstat are the lane tables, lane_of is not read
+            return a.small_replicas != 0 && tables && a.sticket;
+        case SMALL_ACC:  // nothing is stored; the dirty words need their base, the ticket only a phases launch
+            return a.small_replicas != 0 && (!a.acc_zero_n || a.acc_zero) && (a.sticket || !a.phases);
+    }
+    return false;
+}
+
+// LaunchSelect.small: k_select_small over both classes' chunks, finishing inside the launch (every form but SLOTS) or
 // followed by k_small_finish over the rows. With a.ev_start and a.ev_stop both set the kernels go through
 // hipExtLaunchKernelGGL, which binds the events to the dispatch's own begin and end timestamps: the start event to
 // k_select_small, the stop event to the kernel that ends the step. Nothing is recorded on the stream. Without them the
@@ -1522,23 +1562,15 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
     if (a.k != 1 || !a.fused || a.n_fast == 0 || a.n_fast != a.n_pods || lp > 256 || nc == 0 || nc > SMALL_MAX_CHUNKS ||
         (r0.n_chunks && (r0.chunk == 0 || r0.chunk > SMALL_MAX_CHUNK)) ||
         (r1.n_chunks && (r1.chunk == 0 || r1.chunk > SMALL_MAX_CHUNK)) || a.small_slices == 0 ||
-        a.small_slices * lp > SMALL_WG || !a.skeys || !a.sub || !a.sfhi ||
-        (!a.lane_of && !a.small_lanes && !a.small_acc) || ((a.small_lanes || a.small_acc) && !a.small_replicas) ||
-        (a.small_lanes && a.small_acc) || (!a.small_acc && (!a.out || !a.pstat || a.acc_zero_n)) ||
-        (a.acc_zero_n && !a.acc_zero) || (a.small_replicas && !a.sticket && (!a.small_acc || a.phases)) ||
-        (a.prof && (!a.small_replicas || a.ev_start || a.ev_stop)) || (a.phases && !a.prof))
+        a.small_slices * lp > SMALL_WG || !small_args_ok(a))
         return hipErrorInvalidValue;
     dim3 grid(1, nc), block(lp * a.small_slices);
     const bool timed = a.ev_start && a.ev_stop;
-    const hipEvent_t sel_stop = a.small_replicas ? a.ev_stop : nullptr;  // two launches: k_small_finish ends the step
+    const hipEvent_t sel_stop = a.small_form != SMALL_SLOTS ? a.ev_stop : nullptr;  // two launches: k_small_finish ends the step
 #define KG_SMALL_ARGS                                                                                                 \
     a.nodes, a.zones, a.pods, a.n_fast, lp, r0.end, r1.end, r0.chunk, r1.chunk, r1.n_chunks, a.index_base, a.cfg,      \
         a.skeys, a.sub, a.sfhi, a.order, a.small_replicas, a.sticket, a.lane_of, a.n_rows, a.out, a.pstat, a.prof,    \
-        a.small_acc     ? SMALL_FORM_ACC                                                                             \
-        : a.small_lanes ? SMALL_FORM_LANES                                                                           \
-        : a.small_rows4 ? SMALL_FORM_ROWS4                                                                           \
-                        : SMALL_FORM_ROWS,                                                                           \
-        static_cast<uint4*>(a.acc_zero), a.acc_zero_n
+        a.small_form, static_cast<uint4*>(a.acc_zero), a.acc_zero_n
 #define KG_SMALL_WG(PMV, WGV)                                                                                         \
     do {                                                                                                              \
         if (timed)                                                                                                    \
@@ -1555,7 +1587,7 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
             KG_SMALL_WG(PMV, 1024);                                                                                   \
     } while (0)
     if (a.phases) {
-        if ((a.cfg.plugins & 7u) != 7u || block.x <= 512u || !a.small_replicas || timed) return hipErrorInvalidValue;
+        if ((a.cfg.plugins & 7u) != 7u || block.x <= 512u || a.small_form == SMALL_SLOTS || timed) return hipErrorInvalidValue;
         k_select_small<7, 1024, true><<<grid, block, 0, s>>>(KG_SMALL_ARGS);
     } else
     switch (a.cfg.plugins & 7u) {
@@ -1571,7 +1603,7 @@ static hipError_t launch_select_small(const LaunchSelect& a, hipStream_t s) {
 #undef KG_SMALL
 #undef KG_SMALL_WG
 #undef KG_SMALL_ARGS
-    if (a.small_replicas == 0) {
+    if (a.small_form == SMALL_SLOTS) {
         const dim3 fgrid((a.n_rows + SMALL_FIN_WG - 1) / SMALL_FIN_WG);
         if (timed)
             hipExtLaunchKernelGGL(k_small_finish, fgrid, dim3(SMALL_FIN_WG), 0, s, (hipEvent_t) nullptr, a.ev_stop, 0,

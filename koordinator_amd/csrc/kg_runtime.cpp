@@ -25,6 +25,7 @@
 #include <limits>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <tuple>
 #include <string>
 #include <vector>
@@ -287,45 +288,27 @@ struct kg_pods {
     DevBuf<uint64_t> d_ipairs;       // pruned integer lanes: surviving (lane, record) pairs (LaunchSelect.ipairs)
     DevBuf<uint32_t> d_ipair_count;
     size_t ipairs_cap = 0;
-    // accumulators and ticket of the one-launch one-pod-block select's finisher forms: all zero between selects
-    // (ensure_sacc)
+    // accumulators and ticket of the one-launch one-pod-block select's finisher forms (ensure_sacc). INVARIANT: every
+    // word is zero whenever no select runs on the batch and !sacc_dirty; the finisher leaves them so
     DevBuf<uint8_t> d_sacc;
-    bool sacc_dirty = false;
-    // result accumulators of the form without a finisher (LaunchSelect.small_acc; ensure_acc): two parities of
-    // ACC_SLOTS x 16 bytes. The next such launch accumulates into parity acc_par, which is all zero, and zeroes the
-    // acc_dirty[acc_par ^ 1] 16-byte words that the launch before it left in the other one
-    static constexpr uint32_t ACC_SLOTS = 2048;  // replicas x lanes (whole waves) of one launch at most
+    bool sacc_dirty = false;  // the buffer needs the stream memset: regrown, or a call on it failed
+    // result accumulators of the form without a finisher (SMALL_ACC; ensure_acc), under AccParity's invariant
     DevBuf<uint8_t> d_acc;
-    bool acc_clear = false;  // both parities need the stream memset (a failed call)
-    uint32_t acc_par = 0, acc_dirty[2] = {0, 0};
+    AccParity acc;
     DevBuf<uint64_t> d_keys;
     uint32_t k_last = 0, kk_last = 0;
     PinnedBuf<uint64_t> h_keys;    // pinned download staging of the keys [cap][KG_TOPK_MAX]
     DevBuf<uint32_t> d_pstat;   // per pod: KG_ST_UNSUPPORTED / KG_ST_QUOTA of the last select (kg_result_status)
     // Form of the last select's result (set wherever k_last is set). Rows: d_keys [n][kk_last] and d_pstat [n]. Lanes
-    // (res_lanes; the one-launch top-1 select on the batch's own tables, select_local): d_lres holds res_lp keys and,
-    // behind them, res_lp status words, one per lane, and row j takes lane res_lane_of[j]: the host's copy of the row ->
-    // lane table that the select's batch was uploaded with, in h_in. d_keys / d_pstat then hold no result; kg_result_keys
-    // and kg_result_status copy the lane tables into h_lres once per select (res_fetched) and gather on the host. The
-    // next upload rewrites h_in: it drops a lane-form result (result_rows with k_last = 0).
-    // res_acc_r > 0 (with res_lanes): the accumulators are the result. Nothing was stored to d_lres; the readers copy
-    // the res_acc_r x res_lp x 16 bytes at res_acc (the launch's parity of d_acc) into h_lres and fold_acc turns them
-    // into the lane tables in place, once per select. res_stat_at = the status words' place in h_lres, in 64-bit words.
-    // d_lres / h_lres are the last LRES_WORDS words of d_in / h_in, behind every region of pod_layout(cap): no upload
-    // copies that far, and the batch has no allocation more than before.
-    static constexpr uint32_t LRES_LANES = 256, LRES_WORDS = 2 * ACC_SLOTS;  // 64-bit words
-    static_assert(LRES_WORDS >= LRES_LANES + LRES_LANES / 2 && ACC_SLOTS >= LRES_LANES, "the staging holds either form");
-    uint64_t* d_lres = nullptr;
-    uint64_t* h_lres = nullptr;
-    bool res_lanes = false, res_fetched = false;
-    uint32_t res_lp = 0, res_acc_r = 0, res_stat_at = 0;
-    const uint8_t* res_acc = nullptr;
-    const uint8_t* res_lane_of = nullptr;
+    // (res.lanes; the one-launch top-1 select on the batch's own tables, launch_small_select): LaneResult, kg_small.h;
+    // d_keys / d_pstat then hold no result. res.lane_of points into h_in, which the next upload rewrites: it drops a
+    // lane-form result (result_rows with k_last = 0). res.dev / res.host are the last SMALL_LRES_WORDS words of d_in /
+    // h_in, behind every region of pod_layout(cap): no upload copies that far, and the batch has no allocation more.
+    LaneResult res;
     void result_rows(uint32_t k, uint32_t kk) {
         k_last = k;
         kk_last = kk;
-        res_lanes = res_fetched = false;
-        res_acc_r = 0;
+        res.reset();
     }
     DevBuf<uint32_t> d_reason;  // replay: per pod OR of the filter status bits (kg_replay out_reason)
     // The row-list evaluators' scratch, grown on demand: no allocation on the steady path. Each buffer keeps its own
@@ -1566,8 +1549,8 @@ kg_status kg_pods_create(kg_ctx* ctx, uint32_t capacity, kg_pods** out) {
     p->in_bytes = pod_layout(capacity).total;
     hipSetDevice(ctx->device);
     const size_t cap = capacity, keys = (size_t)KG_TOPK_MAX * cap;
-    // the lane tables of a lane-form result (kg_pods.d_lres / h_lres) lie behind the input regions, 256-byte aligned
-    const size_t lres_at = (p->in_bytes + 255) / 256 * 256, in_alloc = lres_at + sizeof(uint64_t) * kg_pods::LRES_WORDS;
+    // the lane tables of a lane-form result (kg_pods.res.dev / host) lie behind the input regions, 256-byte aligned
+    const size_t lres_at = (p->in_bytes + 255) / 256 * 256, in_alloc = lres_at + sizeof(uint64_t) * SMALL_LRES_WORDS;
     const bool ok = !p->d_in.alloc(in_alloc) && !p->h_in.alloc(in_alloc) && !p->d_keys.alloc(keys) &&
                     !p->h_keys.alloc(keys) && !p->d_winners.alloc(cap + 1) && !p->d_step.alloc(64) && !p->d_qst.alloc(cap) &&
                     !p->d_dev_max.alloc(cap) && !p->d_rsv_max.alloc(cap) && !p->d_pref.alloc(cap) &&
@@ -1580,8 +1563,8 @@ kg_status kg_pods_create(kg_ctx* ctx, uint32_t capacity, kg_pods** out) {
         delete p;
         return fail(ctx, KG_OOM, "pod batch of %u", capacity);
     }
-    p->d_lres = reinterpret_cast<uint64_t*>(p->d_in.get() + lres_at);
-    p->h_lres = reinterpret_cast<uint64_t*>(p->h_in.get() + lres_at);
+    p->res.dev = reinterpret_cast<uint64_t*>(p->d_in.get() + lres_at);
+    p->res.host = reinterpret_cast<uint64_t*>(p->h_in.get() + lres_at);
     pod_views(p, 0);
     *out = p;
     return KG_OK;
@@ -1620,7 +1603,7 @@ kg_status kg_pods_upload(kg_pods* p, const kg_pod_columns* cols, uint32_t n) {
     }
     // a result kept per lane is read through the staging's row -> lane table, which is rewritten from here on: the
     // result is gone with it (kg_result_keys: "no selection result" until the next select)
-    if (p->res_lanes) p->result_rows(0, 0);
+    if (p->res.lanes) p->result_rows(0, 0);
     const PodLayout L = pod_layout(n);
     uint8_t* h = p->h_in;
     int64_t* hc = reinterpret_cast<int64_t*>(h + L.cols);
@@ -1924,7 +1907,7 @@ static kg_status derive_lanes(kg_pods* p) {
     } else {
         // row -> lane for the one-pod-block select (a batch with sets or terms does not take it). These are the values
         // kg_pods_upload wrote (same rows, no group ids), and the branch above writes neither table: a lane-form
-        // result of an earlier select (kg_pods.res_lane_of) stays readable across a change of sets or terms
+        // result of an earlier select (kg_pods.res.lane_of) stays readable across a change of sets or terms
         if (n <= 256)
             for (uint32_t t = 0; t < n; t++) h[L.lane + order[t]] = (uint8_t)t;
         if (p->dedup && n_rep <= 256) {
@@ -3167,117 +3150,32 @@ static uint32_t device_cus(kg_ctx* ctx) {
     return ctx->cus > 0 ? (uint32_t)ctx->cus : 0u;
 }
 
-// The one-pod-block fused top-1 select (k_select_small + k_small_finish, kg_kernels.hip): top-1, fused,
-// every lane a fast lane and at most 256 of them, with or without the pod-row reduction. Sets a's geometry for it. A
-// workgroup holds SMALL_COPIES_* copies of the lanes and, with its registers, has a compute unit to itself, so the
-// launch is fastest as one round of workgroups: the chunk lengths are derived from the class lengths so that the
-// chunks number about SMALL_FILL of the device's compute units; between SMALL_MIN_CHUNK and SMALL_MAX_CHUNK records,
-// so a large snapshot runs several rounds, and one that needs more than SMALL_MAX_CHUNKS chunks keeps the general
-// path. Above one wave of lanes a class-1 record counts as two class-0 ones (its chunks are half as long) and the
-// fill is 63/64, with the chunks lengthened while their rounded counts exceed the compute units (one workgroup alone
-// in a second round costs a third more: 46 / 24 records, 259 workgroups, 0.0236 ms). Measured on config 2 at 145
-// lanes (tools/small_phases_by_chunk.py, tools/small_select_ab.py --sweep and --phases, profiles/small_warm/): at 3/4
-// and 7/8 (48 / 36 records, 223 workgroups) a class-1 workgroup took 12.3 us for its loops and a class-0 one 10.2, and
-// the launch ends with its slowest workgroup, through after 13.8 to 14.0 us; at 48 / 24 (251 workgroups) 9.8 against
-// 10.3, the slowest through after 12.6 to 12.7 us. In the sweep (no profiling, 4 repeats, spread 0.0001 to 0.0002 ms)
-// 48 / 36 takes 0.0171-0.0174, 48 / 24 0.0169-0.0170, 48 / 32 0.0166-0.0168, 46 / 26 0.0164-0.0165; which class-1
-// length between 24 and 32 is best differs from run to run, each of them beats 36 in all, and longer chunks at the
-// same ratio lose it again (50 / 28, 54 / 27: as 48 / 36). The headline is bench.py's: 0.0205 -> 0.0187 ms.
-// 256 lanes 0.0194 -> 0.0181 ms, config 4's 100,000 nodes (several rounds) 0.130 -> 0.102. At 64 lanes (16 copies,
-// two or three records each) the loops are short and 28 more workgroups cost more at entry and hand-off than the
-// balance gains, 0.0121 -> 0.0127: one wave of lanes keeps 3/4 and 7/8. So does a table with F_BIG records: their
-// inline integer path decides which workgroup is last, by where the chunk borders fall (0.4 % F_BIG records: 0.0447
-// to 0.0489 ms over class-0 lengths 37 to 40 at either ratio, 0.0555 at the new rule's own choice against 0.0463;
-// 0.2 %: 0.0408 either way), and a fuller chip leaves it no idle neighbours. KG_NO_SMALL_SELECT (read per
-// call) keeps the general path too; KG_SMALL_CHUNKS="c0,c1,copies" sets the geometry (measurement aid).
-// threads that the copies of the lanes may fill (512: the launch-bound variant without scratch; 1024: the spilling one)
-constexpr uint32_t SMALL_COPIES_WG = 1024, SMALL_BIG_DEN = 250, SMALL_BIG_EVEN_DEN = 400;
-constexpr uint32_t SMALL_MIN_CHUNK = 8, SMALL_FILL_NUM = 63, SMALL_FILL_DEN = 64;
-// The finish inside the launch: the workgroups fold into SMALL_REPLICAS replicas of the accumulators, whatever the chunk
-// count. Measured (tools/small_select_ab.py --replicas, profiles/small_fused/replicas_*.jsonl, ms per select by replica
-// count 1 / 4 / 8 / 16 / 32 / 64 / one per chunk, then the two launches): config 2 at 145 lanes (223 chunks) 0.0185 /
-// 0.0176 / 0.0182 / 0.0185 / 0.0197 / 0.0221 / 0.0343, two launches 0.0248; 64 lanes 0.0134 / 0.0120 / 0.0120 / 0.0122 /
-// 0.0126 / 0.0135 / 0.0178, 0.0151; 256 lanes 0.0191 / 0.0190 / 0.0197 / 0.0204 / 0.0220 / 0.0254 / 0.0422, 0.0303;
-// config 4's 100,000 nodes at 145 lanes (1,667 chunks) 0.1350 / 0.1332 / 0.1333 / 0.1337 / 0.1349 / 0.1381 / 0.2615,
-// 0.1798. Hundreds of workgroups adding to one address cost under 0.001 ms; every replica more is read by the lone
-// finisher. KG_SMALL_REPLICAS (read per call) sets the count, also past the row gate: the tool and the tests.
-// Without a finisher (SMALL_ACC_REPLICAS; profiles/small_acc/replicas_config2.jsonl, config 2 at 145 lanes, ms per
-// select by replica count 1 / 2 / 4 / 8): 0.0156 / 0.0133 / 0.0122 / 0.0121-0.0122 without profiling, 0.0160 / 0.0143 /
-// 0.0142 / 0.0142 with it: contention at the end of the launch is on the critical path, and 8 is within the spread of 4.
-// Row gate (--rows, profiles/small_fused/rows_breakeven.jsonl; 145 lanes, one launch / two launches): 10,000 rows
-// 0.0180 / 0.0250 ms, 50,000 rows 0.0259 / 0.0248, 200,000 rows 0.0558 / 0.0252: the lone finisher writes n_rows x 12
-// bytes, the break-even interpolates to about 45,000 rows, the one launch is taken up to SMALL_FUSED_MAX_ROWS. The gate
-// is the row form's: a result kept per lane (lanes_ok below) stores no row, and its one launch measured 0.0149 / 0.0150 /
-// 0.0151 ms at 10,000 / 50,000 / 200,000 rows (tools/small_reader_ab.py, profiles/small_lanes/reader_ab.jsonl).
-// The form without a finisher (lanes_ok and no KG_SMALL_FINISHER, read per call: the accumulators are the result,
-// DESIGN.md §4) has its own replica count, SMALL_ACC_REPLICAS: no finisher pays per replica, the reader folds them.
-// The count is capped by what the batch's accumulators and staging hold (kg_pods::ACC_SLOTS).
-constexpr uint32_t SMALL_REPLICAS = 4, SMALL_ACC_REPLICAS = 4, SMALL_FUSED_MAX_ROWS = 32768;
-static bool select_small(const kg_snap* s, LaunchSelect& a, bool lanes_ok) {
-    if (a.k != 1 || !a.fused || a.n_fast == 0 || a.n_fast != a.n_pods || a.n_fast > 256) return false;
-    if (std::getenv("KG_NO_SMALL_SELECT")) return false;
-    // F_BIG gate: the F_BIG records run inline on the integer path behind the fast records of the wave that meets
-    // them, pruned by that wave's best fast key only, and the launch ends with its slowest workgroup; k_big_sel spreads
-    // them over the chip and prunes with the final key. Measured (tools/small_select_ab.py --shares; this
-    // path / the general one, ms): 0.2 % F_BIG records 0.048 / 0.066, 0.4 % 0.054 / 0.068, 0.6 % 0.075 / 0.071, 1 %
-    // 0.075 / 0.075, 15 % 0.096 / 0.079. The break-even lies between 0.4 % and 0.6 %: the path is taken up to 1 record
-    // in SMALL_BIG_DEN (count at the last upload / row update; records that turn F_BIG on the device later are still
-    // evaluated). KG_SMALL_ALLOW_BIG (read per call) lifts the gate: the A/B tool and the tests
-    if ((uint64_t)s->n_big_est * SMALL_BIG_DEN > s->n && !std::getenv("KG_SMALL_ALLOW_BIG")) return false;
-    const uint32_t lp = (a.n_fast + 63) / 64 * 64;
-    const uint32_t len0 = a.range[0].end - a.range[0].begin, len1 = a.range[1].end - a.range[1].begin;
-    const uint32_t cus = std::max<uint32_t>(device_cus(s->ctx), 8u);
-    // one wave of lanes, or F_BIG records above 1 in SMALL_BIG_EVEN_DEN: 3/4 and 7/8, see above
-    const bool narrow = lp <= 64 || (uint64_t)s->n_big_est * SMALL_BIG_EVEN_DEN > s->n;
-    const uint32_t want = std::max<uint32_t>(1u, narrow ? cus * 7 / 8 : cus * SMALL_FILL_NUM / SMALL_FILL_DEN);
-    // a class-1 chunk is rn / rd as long as a class-0 one; the work in 1 / rn of a class-0 record
-    const uint32_t rn = narrow ? 3 : 1, rd = narrow ? 4 : 2;
-    const uint64_t work = (uint64_t)len0 * rn + (uint64_t)len1 * rd;
-    const auto chunk1_of = [&](uint32_t c0) { return std::max<uint32_t>(1u, narrow ? c0 * 3 / 4 : (c0 + 1) / 2); };
-    const auto chunks_at = [&](uint32_t c0) { return (len0 + c0 - 1) / c0 + (len1 + chunk1_of(c0) - 1) / chunk1_of(c0); };
-    uint32_t chunk[2];
-    chunk[0] = (uint32_t)std::min<uint64_t>(SMALL_MAX_CHUNK, std::max<uint64_t>(SMALL_MIN_CHUNK, (work + (uint64_t)rn * want - 1) / ((uint64_t)rn * want)));
-    // the rounding of the two chunk counts may take them past the compute units: no second round for a few workgroups
-    while (!narrow && chunk[0] < SMALL_MAX_CHUNK && chunks_at(chunk[0]) > cus && chunks_at(chunk[0]) < 2 * cus) chunk[0]++;
-    chunk[1] = chunk1_of(chunk[0]);
-    a.small_slices = SMALL_COPIES_WG / lp;
-    if (const char* e = std::getenv("KG_SMALL_CHUNKS")) {
-        unsigned c0 = 0, c1 = 0, sl = 0;
-        if (std::sscanf(e, "%u,%u,%u", &c0, &c1, &sl) == 3 && c0 >= 1 && c0 <= SMALL_MAX_CHUNK && c1 >= 1 &&
-            c1 <= SMALL_MAX_CHUNK && sl >= 1 && sl * lp <= SMALL_WG) {
-            chunk[0] = c0;
-            chunk[1] = c1;
-            a.small_slices = sl;
-        }
-    }
-    SelectRange r[2] = {a.range[0], a.range[1]};
-    for (int c = 0; c < 2; c++) {
-        r[c].chunk = chunk[c];
-        r[c].n_chunks = (r[c].end - r[c].begin + chunk[c] - 1) / chunk[c];
-        r[c].part0 = 0;
-    }
-    if (r[0].n_chunks + r[1].n_chunks == 0 || r[0].n_chunks + r[1].n_chunks > SMALL_MAX_CHUNKS) return false;
-    a.range[0] = r[0];
-    a.range[1] = r[1];
+// The plan of the one-pod-block fused top-1 select for launch a (k_select_small + k_small_finish, kg_kernels.hip),
+// with or without the pod-row reduction: small_plan's rules (kg_small.h) on DESIGN.md §4's measurements. A plan that
+// takes the path is written into a. The switches are read only for a shape that can take the path. lanes_ok: only
+// kg_result_keys / kg_result_status read the result (d_out is the batch's own d_keys; a sharded select's lies in the
+// buffer that the all-gather sends). aligned16, for the finisher's 16-byte row stores and 4-byte lane loads: the lane
+// tables are 256-byte aligned regions of the batch's input buffer, d_pstat and a batch's own d_keys are allocations; a
+// sharded select's d_out lies n x world keys into the gather buffer, 8-byte aligned only when that is odd.
+static SmallPlan plan_small_select(const kg_snap* s, const kg_pods* p, LaunchSelect& a, const uint8_t* lane_of,
+                                   const uint64_t* d_out, SmallSwitches& sw) {
+    const auto aligned16 = [](const void* q) { return reinterpret_cast<uintptr_t>(q) % 16u == 0; };
+    SmallShape in{a.k, a.fused, a.n_pods, a.n_fast, a.n_rows, {a.range[0].end - a.range[0].begin, a.range[1].end - a.range[1].begin},
+                  s->n_big_est, s->n, 0, false, aligned16(lane_of) && aligned16(d_out) && aligned16(p->d_pstat.get())};
+    // the one-pod-block select writes every row of out and pstat through the lane tables: not with sets or terms
+    if (p->lanes_split() || !small_shape_ok(in)) return {};
+    sw = small_switches();
+    in.cus = device_cus(s->ctx);
+    in.lanes_ok = d_out == p->d_keys.get() && !sw.row_results;
+    const SmallPlan pl = small_plan(in, sw);
+    if (!pl.take) return pl;
+    for (int c = 0; c < 2; c++) a.range[c] = {a.range[c].begin, a.range[c].end, pl.chunk[c], pl.n_chunks[c], 0};
     a.small = true;
-    // The finish inside the launch (small_replicas > 0), unless KG_NO_SMALL_FUSED_FINISH (read per call) or, in the row
-    // form, the row count keeps the two launches: a lone finisher writes all n_rows x 12 bytes. The lane form
-    // (lanes_ok: the caller can keep the result per lane) stores no row and takes the one launch at any row count.
-    const uint32_t nc = r[0].n_chunks + r[1].n_chunks;
-    a.small_replicas = 0;
-    if (!std::getenv("KG_NO_SMALL_FUSED_FINISH")) {
-        const bool acc = lanes_ok && !std::getenv("KG_SMALL_FINISHER");
-        uint32_t rep = acc ? SMALL_ACC_REPLICAS : lanes_ok || a.n_rows <= SMALL_FUSED_MAX_ROWS ? SMALL_REPLICAS : 0u;
-        if (const char* e = std::getenv("KG_SMALL_REPLICAS")) {  // also past the row gate
-            unsigned v = 0;
-            if (std::sscanf(e, "%u", &v) == 1 && v >= 1) rep = v;
-        }
-        a.small_replicas = std::min(rep, nc);  // more replicas than chunks: one chunk each
-        if (acc) a.small_replicas = std::min(a.small_replicas, kg_pods::ACC_SLOTS / lp);
-        a.small_acc = acc && a.small_replicas != 0;
-    }
-    a.small_lanes = lanes_ok && a.small_replicas != 0 && !a.small_acc;
-    return true;
+    a.small_slices = pl.slices;
+    a.small_form = pl.form;
+    a.small_replicas = pl.replicas;
+    a.lane_of = lane_of;
+    return pl;
 }
 
 // The accumulators and the ticket of the one-launch form (LaunchSelect.skeys / sfhi / sub / sticket): a buffer of
@@ -3286,8 +3184,8 @@ static bool select_small(const kg_snap* s, LaunchSelect& a, bool lanes_ok) {
 // buffer is allocated or regrown, and again before the first select after one that returned an error (sacc_dirty);
 // k_select_small's finisher reads every accumulator word by an exchange with zero and stores zero to the ticket, so a
 // steady-state step zeroes nothing from the host. All words being zero, the next launch may lay the arrays out for
-// another replica or lane count. The form without a finisher (LaunchSelect.small_acc) has accumulators of its own
-// under another rule (ensure_acc); a batch may switch between the forms from call to call.
+// another replica or lane count. The form without a finisher (SMALL_ACC) has accumulators of its own under another
+// rule (AccParity, ensure_acc); a batch may switch between the forms from call to call.
 constexpr size_t SACC_HEAD = 128;
 
 // Drains the context's device-clock pool (kg_ctx.d_prof): k_prof_fold folds the region of every launch since the last
@@ -3346,7 +3244,7 @@ static kg_status prof_pool(kg_ctx* ctx) {
 
 // A region of nc pairs of the context's device-clock pool (kg_ctx.d_prof) for a profiled one-launch select of nc
 // workgroups; *out stays nullptr when the device reports no wall clock rate: the caller then keeps the bound event
-// pair, as it would for a region that does not fit in an empty pool (no launch has one: select_small keeps nc at most
+// pair, as it would for a region that does not fit in an empty pool (no launch has one: small_plan keeps nc at most
 // SMALL_MAX_CHUNKS, asserted against PROF_PAIRS). A full launch table, or a pool without nc free pairs, is drained
 // first. The caller counts the region (prof_take) once its launch succeeded.
 static kg_status ensure_prof(kg_ctx* ctx, uint32_t nc, uint64_t** out) {
@@ -3369,17 +3267,16 @@ static void prof_take(kg_ctx* ctx, uint32_t nc, bool all_end) {
     ctx->prof_used += nc;
 }
 
-// KG_SMALL_PHASES=<file> (read per call; measurement aid, tools/small_select_ab.py --phases): the one-launch select of
+// KG_SMALL_PHASES=<file> (SmallSwitches.phases; measurement aid, tools/small_select_ab.py --phases): the one-launch select of
 // config 2's shape (all three plugins, the 1,024-thread variant) runs k_select_small's PH instantiation; after the
 // launch the stream is synchronised and one record is appended to the file: uint64 workgroup count, then four uint64
 // clock readings per workgroup (entry, loops done, ticket drawn, rows stored or 0; without a finisher: entry, loops done,
 // result atomics complete, and the launch's end in the workgroup that was last, else 0). A fifth reading per workgroup,
 // "pod operands ready", goes to <file>.ops in records of its own (workgroup count, then one reading each). Other shapes
 // ignore the switch.
-static const char* small_phases_file(const LaunchSelect& a, uint32_t lp) {
-    const char* f = std::getenv("KG_SMALL_PHASES");
-    if (!f || !*f || !a.small_replicas || (a.cfg.plugins & 7u) != 7u || a.small_slices * lp <= 512u) return nullptr;
-    return f;
+static const char* small_phases_file(const SmallSwitches& sw, const LaunchSelect& a, uint32_t lp) {
+    const bool shape = a.small_form != SMALL_SLOTS && (a.cfg.plugins & 7u) == 7u && a.small_slices * lp > 512u;
+    return shape ? sw.phases : nullptr;
 }
 
 static kg_status small_phases_write(kg_ctx* ctx, const char* file, uint32_t nc) {
@@ -3417,24 +3314,101 @@ static kg_status ensure_sacc(kg_pods* p, uint32_t replicas, uint32_t lp) {
     return KG_OK;
 }
 
-// The result accumulators of the form without a finisher (LaunchSelect.small_acc; kg_pods.d_acc). INVARIANT: when no
-// select runs on the batch, parity acc_par is all zero and the other one is zero past its first acc_dirty 16-byte
-// words. A launch accumulates into acc_par and zeroes the other parity's dirty words at its entry (same-stream order:
-// the launch that dirtied them, and the copy that read them, are through); select_local then swaps the parities. The
-// arrays of a launch start at the parity's base whatever its replica and lane counts, so the dirty words are a
-// prefix. The memset establishes the invariant at allocation and after a call that returned an error.
+// The result accumulators of the form without a finisher (SMALL_ACC; kg_pods.d_acc, kg_pods.acc): the memset
+// establishes AccParity's invariant at allocation and after a call that returned an error.
 static kg_status ensure_acc(kg_pods* p) {
     kg_ctx* ctx = p->ctx;
-    constexpr size_t bytes = 2 * (size_t)kg_pods::ACC_SLOTS * 16;
+    constexpr size_t bytes = 2 * (size_t)SMALL_ACC_SLOTS * 16;
     if (!p->d_acc) {
         HIP_TRY(ctx, p->d_acc.alloc(bytes));
-        p->acc_clear = true;
+        p->acc = AccParity{};  // a new buffer: clear
     }
-    if (p->acc_clear) {
+    if (p->acc.clear) {
         HIP_TRY(ctx, hipMemsetAsync(p->d_acc, 0, bytes, ctx->stream));
-        p->acc_clear = false;
-        p->acc_dirty[0] = p->acc_dirty[1] = 0;
+        p->acc.cleared();
     }
+    return KG_OK;
+}
+
+// The one-pod-block select of select_local's launch a, where its plan takes the path (else no value: nothing is
+// changed and the general path follows): one launch (or two) writes every row of d_out and d_pstat, every lane of res.dev, or
+// leaves the accumulators as the result: no memset, no side stream, no expansion. Binds the planned form's buffers,
+// takes the bracket, launches, and commits or fails the batch state (AccParity, sacc_dirty, LaneResult).
+static std::optional<kg_status> launch_small_select(kg_snap* s, kg_pods* p, LaunchSelect& a, uint64_t* d_out, bool dd) {
+    kg_ctx* ctx = s->ctx;
+    SmallSwitches sw;
+    const SmallPlan pl = plan_small_select(s, p, a, dd ? p->d_rlane : p->d_lane, d_out, sw);
+    if (!pl.take) return std::nullopt;
+    const uint32_t lp = small_lp(a.n_fast), nc = pl.n_chunks[0] + pl.n_chunks[1];
+    const size_t slots = (size_t)(pl.replicas ? pl.replicas : nc) * lp;  // ACC: at most SMALL_ACC_SLOTS (small_plan)
+    const char* phases = small_phases_file(sw, a, lp);
+    const bool ticket = pl.form == SMALL_ACC ? phases != nullptr : pl.form != SMALL_SLOTS;
+    kg_status st = KG_OK;
+    if (pl.form == SMALL_SLOTS) {
+        HIP_TRY(ctx, grow(ctx, p->d_partial, 2 * slots));
+        a.skeys = p->d_partial;
+        a.sub = reinterpret_cast<uint32_t*>(p->d_partial + slots);
+        a.sfhi = a.sub + slots;
+    } else {  // [replicas][lp] keys, fast-key high words, unsupported bounds, contiguous in that order
+        st = pl.form == SMALL_ACC ? ensure_acc(p) : ensure_sacc(p, pl.replicas, lp);
+        if (st != KG_OK) return st;
+        uint8_t* acc = p->d_sacc + SACC_HEAD;
+        if (pl.form == SMALL_ACC) {
+            const AccParity::Next nx = p->acc.next();
+            acc = p->d_acc + nx.mine;
+            a.acc_zero = p->d_acc + nx.other;
+            a.acc_zero_n = nx.zero_n;
+        }
+        a.skeys = reinterpret_cast<uint64_t*>(acc);
+        a.sfhi = reinterpret_cast<uint32_t*>(a.skeys + slots);
+        a.sub = a.sfhi + slots;
+    }
+    if (pl.form == SMALL_LANES) {  // lp <= SMALL_MAX_LANES
+        a.out = p->res.dev;
+        a.pstat = reinterpret_cast<uint32_t*>(p->res.dev + lp);
+    }
+    // kernel-time bracket (kg_profile_read). One launch: the kernel times itself with the device clock (a.prof: a
+    // region of the context's pool, one pair per workgroup, ensure_prof), the launch is the plain one and the host
+    // only counts the region, once the launch succeeded. Two launches, a device without a wall clock
+    // rate, or KG_PROFILE_BOUND_EVENTS (the tool and the tests compare both brackets): the launch carries a pooled
+    // event pair itself (LaunchSelect.ev_start / ev_stop), nothing is recorded on the stream. The pair goes on ev_live
+    // only once the launch took it; every failure hands it back to the pool
+    if (phases) {  // a launch of the measurement aid has no bracket: its pairs are the scratch ones in d_phases
+        HIP_TRY(ctx, grow(ctx, ctx->d_phases, (size_t)nc * 7));
+        if (pl.form == SMALL_ACC) st = ensure_sacc(p, 1, lp);  // the ticket that only this instantiation draws
+        if (st != KG_OK) return st;
+        a.phases = true;
+        a.prof = ctx->d_phases;
+    } else if (ctx->profiling && pl.form != SMALL_SLOTS && !sw.bound_events) {
+        st = ensure_prof(ctx, nc, &a.prof);
+    }
+    if (ticket) a.sticket = reinterpret_cast<uint32_t*>(p->d_sacc.get());  // zero between launches
+    if (st == KG_OK && !a.prof) st = bracket_take(ctx, &a.ev_start, &a.ev_stop);
+    if (st == KG_OK) {
+        const hipError_t le = launch_select(a, ctx->stream);
+        if (le != hipSuccess) {
+            bracket_drop(ctx, a.ev_start, a.ev_stop);
+            // the region is not counted and goes to the next launch: zero, whatever this one wrote
+            if (a.prof && !phases) hipMemsetAsync(a.prof, 0, 2 * sizeof(uint64_t) * nc, ctx->stream);
+            st = fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR, "launch_select(a, ctx->stream): %s",
+                      hipGetErrorString(le));
+        } else if (a.prof && !phases) {
+            prof_take(ctx, nc, pl.form == SMALL_ACC);
+        } else if (a.ev_start) {
+            ctx->ev_live.emplace_back(a.ev_start, a.ev_stop);
+        }
+        if (st == KG_OK && phases) st = small_phases_write(ctx, phases, nc);
+    }
+    if (st != KG_OK) {  // a failed call may have left a launch half done: what it used is zeroed before the next one
+        if (pl.form == SMALL_ACC) p->acc.failed();
+        if (ticket) p->sacc_dirty = true;
+        return st;
+    }
+    // the launch is on the stream: only now the batch claims a lane-form result (result_rows before: rows), and the
+    // launch's parity is the dirty one
+    if (pl.form == SMALL_LANES || pl.form == SMALL_ACC)
+        p->res.claim(lp, p->h_in.get() + (a.lane_of - p->d_in.get()), pl.form == SMALL_ACC ? pl.replicas : 0u, a.skeys);
+    if (pl.form == SMALL_ACC) p->acc.launched((uint32_t)slots);
     return KG_OK;
 }
 
@@ -3508,108 +3482,7 @@ static kg_status select_local(kg_snap* s, kg_pods* p, uint32_t k, uint64_t* d_ou
     const uint32_t n_lanes = dd ? p->n_rep_plain : p->n_plain_lanes, n_lanes_fast = dd ? p->n_rep_plain_fast : p->n_plain_fast;
     LaunchSelect a = make_select(s, p->dev, dd ? p->d_rorder : p->d_order, n_lanes, n_lanes_fast, p->n, kk, true, d_out,
                                  nullptr, p->d_pstat, &parts);
-    // the one-pod-block select writes every row of out and pstat through the lane tables: not with sets or terms.
-    // Where only kg_result_keys / kg_result_status read the result (d_out is the batch's own d_keys; a sharded select's
-    // lies in the buffer that the all-gather sends) the one launch keeps it per lane and those two expand the rows on
-    // the host (kg_pods.res_lanes). KG_SMALL_ROW_RESULTS (read per call) keeps the rows: the A/B tool and the tests
-    const bool lanes_ok = d_out == p->d_keys.get() && !std::getenv("KG_SMALL_ROW_RESULTS");
-    if (!p->lanes_split() && select_small(s, a, lanes_ok)) {
-        // one launch (or two) writes every row of d_out and d_pstat, or every lane of d_lres: no memset, no side stream,
-        // no expansion
-        const uint32_t lp = (a.n_fast + 63) / 64 * 64;
-        kg_status st;
-        const size_t acc_slots = (size_t)a.small_replicas * lp;  // small_acc: at most ACC_SLOTS (select_small)
-        if (a.small_acc) {
-            st = ensure_acc(p);
-            if (st != KG_OK) return st;
-            uint8_t* const mine = p->d_acc + (size_t)p->acc_par * kg_pods::ACC_SLOTS * 16;
-            a.skeys = reinterpret_cast<uint64_t*>(mine);
-            a.sfhi = reinterpret_cast<uint32_t*>(a.skeys + acc_slots);
-            a.sub = a.sfhi + acc_slots;
-            a.acc_zero = p->d_acc + (size_t)(p->acc_par ^ 1u) * kg_pods::ACC_SLOTS * 16;
-            a.acc_zero_n = p->acc_dirty[p->acc_par ^ 1u];
-        } else if (a.small_replicas) {
-            st = ensure_sacc(p, a.small_replicas, lp);
-            if (st != KG_OK) return st;
-            const size_t slots = acc_slots;
-            a.sticket = reinterpret_cast<uint32_t*>(p->d_sacc.get());
-            a.skeys = reinterpret_cast<uint64_t*>(p->d_sacc + SACC_HEAD);
-            a.sfhi = reinterpret_cast<uint32_t*>(a.skeys + slots);
-            a.sub = a.sfhi + slots;
-        } else {
-            const size_t slots = (size_t)(a.range[0].n_chunks + a.range[1].n_chunks) * lp;
-            HIP_TRY(ctx, grow(ctx, p->d_partial, 2 * slots));
-            a.skeys = p->d_partial;
-            a.sub = reinterpret_cast<uint32_t*>(p->d_partial + slots);
-            a.sfhi = a.sub + slots;
-        }
-        a.lane_of = dd ? p->d_rlane : p->d_lane;
-        // The finisher's 16-byte row stores and 4-byte lane loads need aligned tables. The lane tables are 256-byte
-        // aligned regions of the batch's input buffer (pod_layout), d_pstat and a batch's own d_keys are allocations;
-        // a sharded select's d_out lies n x world keys into the gather buffer, 8-byte aligned only when that is odd:
-        // checked here, and such a launch stores its rows one by one
-        const auto aligned16 = [](const void* q) { return reinterpret_cast<uintptr_t>(q) % 16u == 0; };
-        a.small_rows4 = aligned16(a.lane_of) && aligned16(d_out) && aligned16(p->d_pstat.get());
-        if (a.small_lanes) {  // lp <= LRES_LANES (select_small: at most 256 lanes)
-            a.out = p->d_lres;
-            a.pstat = reinterpret_cast<uint32_t*>(p->d_lres + lp);
-        }
-        // kernel-time bracket (kg_profile_read). One launch: the kernel times itself with the device clock (a.prof: a
-        // region of the context's pool, one pair per workgroup, ensure_prof), the launch is the plain one and the host
-        // only counts the region, once the launch succeeded. Two launches, a device without a wall clock
-        // rate, or KG_PROFILE_BOUND_EVENTS (read per call: the tool and the tests compare both brackets): the launch
-        // carries a pooled event pair itself (LaunchSelect.ev_start / ev_stop), nothing is recorded on the stream. The
-        // pair goes on ev_live only once the launch took it; every failure hands it back to the pool
-        const uint32_t nc = a.range[0].n_chunks + a.range[1].n_chunks;
-        const char* phases = small_phases_file(a, lp);
-        st = KG_OK;
-        if (phases) {  // a launch of the measurement aid has no bracket: its pairs are the scratch ones in d_phases
-            HIP_TRY(ctx, grow(ctx, ctx->d_phases, (size_t)nc * 7));
-            if (a.small_acc) {  // the ticket that only this instantiation draws: the finisher forms', zero between launches
-                st = ensure_sacc(p, 1, lp);
-                if (st != KG_OK) return st;
-                a.sticket = reinterpret_cast<uint32_t*>(p->d_sacc.get());
-            }
-            a.phases = true;
-            a.prof = ctx->d_phases;
-        } else if (ctx->profiling && a.small_replicas && !std::getenv("KG_PROFILE_BOUND_EVENTS")) {
-            st = ensure_prof(ctx, nc, &a.prof);
-        }
-        if (st == KG_OK && !a.prof) st = bracket_take(ctx, &a.ev_start, &a.ev_stop);
-        if (st == KG_OK) {
-            const hipError_t le = launch_select(a, ctx->stream);
-            if (le != hipSuccess) {
-                bracket_drop(ctx, a.ev_start, a.ev_stop);
-                // the region is not counted and goes to the next launch: zero, whatever this one wrote
-                if (a.prof && !phases) hipMemsetAsync(a.prof, 0, 2 * sizeof(uint64_t) * nc, ctx->stream);
-                st = fail(ctx, le == hipErrorOutOfMemory ? KG_OOM : KG_DEVICE_ERROR, "launch_select(a, ctx->stream): %s",
-                          hipGetErrorString(le));
-            } else if (a.prof && !phases) {
-                prof_take(ctx, nc, a.small_acc);
-            } else if (a.ev_start) {
-                ctx->ev_live.emplace_back(a.ev_start, a.ev_stop);
-            }
-            if (st == KG_OK && phases) st = small_phases_write(ctx, phases, nc);
-        }
-        // the batch claims a lane-form result only once its launch is on the stream (result_rows above: rows)
-        if (st == KG_OK && (a.small_lanes || a.small_acc)) {
-            p->res_lanes = true;
-            p->res_lp = lp;
-            p->res_stat_at = lp;
-            p->res_lane_of = p->h_in.get() + (a.lane_of - p->d_in.get());
-        }
-        if (st == KG_OK && a.small_acc) {  // the launch is on the stream: its parity is dirty, the other one clean
-            p->res_acc_r = a.small_replicas;
-            p->res_acc = reinterpret_cast<const uint8_t*>(a.skeys);
-            p->acc_dirty[p->acc_par] = (uint32_t)acc_slots;
-            p->acc_dirty[p->acc_par ^ 1u] = 0;
-            p->acc_par ^= 1u;
-        }
-        // a failed call may have left a launch half done: the accumulators are zeroed again before the next one
-        if (st != KG_OK && a.small_acc) p->acc_clear = true;
-        if (st != KG_OK && a.small_replicas && (!a.small_acc || phases)) p->sacc_dirty = true;
-        return st;
-    }
+    if (const auto small = launch_small_select(s, p, a, d_out, dd)) return *small;
     HIP_TRY(ctx, hipMemsetAsync(p->d_pstat, 0, sizeof(uint32_t) * p->n, ctx->stream));
     // the set and term lanes insert into zeroed rows by atomics, whichever form the other lanes' launch takes
     if (p->lanes_split()) HIP_TRY(ctx, hipMemsetAsync(d_out, 0, sizeof(uint64_t) * kk * p->n, ctx->stream));
@@ -3684,48 +3557,18 @@ kg_status kg_eval_select(kg_snap* s, kg_pods* p, uint32_t k) {
     return select_local(s, p, k, p->d_keys);
 }
 
-// A lane-form result (kg_pods.res_lanes) on the host: one copy of the res_lp keys and status words into the pinned
-// staging and the stream sync of every result read; the staging then serves every further read of the same select.
-// res_acc_r > 0: the copy is the launch's parity of the accumulators, res_acc_r x res_lp x 16 bytes, and fold_acc makes
-// the lane tables of it.
-static void fold_acc(kg_pods* p);
+// A lane-form result (kg_pods.res) on the host: one copy of the lane tables, or of the launch's parity of the
+// accumulators, into the pinned staging and the stream sync of every result read; LaneResult::fold makes the lane
+// tables of accumulators. The staging then serves every further read of the same select.
 static kg_status fetch_lanes(kg_pods* p) {
     kg_ctx* ctx = p->ctx;
-    if (!p->res_fetched) {
-        if (p->res_acc_r)
-            HIP_TRY(ctx, hipMemcpyAsync(p->h_lres, p->res_acc, (size_t)16 * p->res_acc_r * p->res_lp, hipMemcpyDeviceToHost,
-                                        ctx->stream));
-        else
-            HIP_TRY(ctx, hipMemcpyAsync(p->h_lres, p->d_lres, (sizeof(uint64_t) + sizeof(uint32_t)) * p->res_lp,
-                                        hipMemcpyDeviceToHost, ctx->stream));
-    }
+    LaneResult& r = p->res;
+    if (!r.fetched)
+        HIP_TRY(ctx, hipMemcpyAsync(r.host, r.acc_r ? (const void*)r.acc : r.dev, r.fetch_bytes(), hipMemcpyDeviceToHost,
+                                    ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (!p->res_fetched && p->res_acc_r) fold_acc(p);
-    p->res_fetched = true;
+    r.fold();
     return KG_OK;
-}
-
-// The staged accumulators of a select without a finisher, [r][lp] keys, [r][lp] fast-key high words, [r][lp] unsupported
-// bounds, become the lane tables in place: per lane the maximum over the replicas, and k_small_finish's status rule.
-// The keys of replica 0 are the key table; the status words take the place of replica 0's high words (res_stat_at).
-static void fold_acc(kg_pods* p) {
-    const uint32_t r = p->res_acc_r, lp = p->res_lp;
-    uint64_t* keys = p->h_lres;
-    uint32_t* fhi = reinterpret_cast<uint32_t*>(keys + (size_t)r * lp);
-    const uint32_t* ub = fhi + (size_t)r * lp;
-    for (uint32_t j = 0; j < lp; j++) {
-        uint64_t k = keys[j];
-        uint32_t f = fhi[j], u = ub[j];
-        for (uint32_t q = 1; q < r; q++) {
-            const size_t at = (size_t)q * lp + j;
-            k = std::max(k, keys[at]);
-            f = std::max(f, fhi[at]);
-            u = std::max(u, ub[at]);
-        }
-        keys[j] = k;
-        fhi[j] = u != 0u && u > f ? KG_ST_UNSUPPORTED : 0u;
-    }
-    p->res_stat_at = r * lp;
 }
 
 kg_status kg_result_keys(kg_pods* p, uint64_t* out) {
@@ -3734,11 +3577,11 @@ kg_status kg_result_keys(kg_pods* p, uint64_t* out) {
     std::lock_guard<std::mutex> g(ctx->mu);
     if (p->k_last == 0) return fail(ctx, KG_INVALID_ARG, "no selection result");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (p->res_lanes) {  // k_last == kk_last == 1; every table entry is a lane below res_lp
+    if (p->res.lanes) {  // k_last == kk_last == 1; every table entry is a lane below res.lp
         kg_status st = fetch_lanes(p);
         if (st != KG_OK) return st;
-        const uint64_t* lk = p->h_lres;
-        const uint8_t* lane = p->res_lane_of;
+        const uint64_t* lk = p->res.host;
+        const uint8_t* lane = p->res.lane_of;
         for (uint32_t j = 0; j < p->n; j++) out[j] = lk[lane[j]];
         return KG_OK;
     }
@@ -3776,11 +3619,11 @@ kg_status kg_result_status(kg_pods* p, uint32_t* out) {
     std::lock_guard<std::mutex> g(ctx->mu);
     if (p->k_last == 0) return fail(ctx, KG_INVALID_ARG, "no selection result");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (p->res_lanes) {
+    if (p->res.lanes) {
         kg_status st = fetch_lanes(p);
         if (st != KG_OK) return st;
-        const uint32_t* ls = reinterpret_cast<const uint32_t*>(p->h_lres + p->res_stat_at);
-        const uint8_t* lane = p->res_lane_of;
+        const uint32_t* ls = p->res.status();
+        const uint8_t* lane = p->res.lane_of;
         for (uint32_t j = 0; j < p->n; j++) out[j] = ls[lane[j]];
         return KG_OK;
     }

@@ -1,5 +1,6 @@
 """The form of the one-launch top-1 select that has no finisher: the accumulators are the result (k_select_small with
-SMALL_FORM_ACC, kg_kernels.hip; select_small, ensure_acc, fetch_lanes and fold_acc in kg_runtime.cpp).
+SMALL_ACC, kg_kernels.hip; launch_small_select, ensure_acc and fetch_lanes in kg_runtime.cpp, AccParity and fold_acc in
+kg_small.h).
 Slice 0 of every workgroup folds into one of two parities of the batch's result accumulators and leaves; nothing reads
 them back on the device. kg_result_keys / kg_result_status copy the launch's parity, fold the replicas, apply the status
 rule and gather the rows on the host. Launch N zeroes what launch N - 1 left in the other parity, so the cases below are

@@ -1,7 +1,10 @@
-"""The lane form of the one-launch top-1 select's result (k_select_small with SMALL_FORM_LANES, select_local and
-kg_result_keys / kg_result_status in kg_runtime.cpp). A kg_eval_select on the batch's own tables keeps one key and one
-status word per lane on the device; the two readers copy those and expand the rows on the host through the row -> lane
-table of the upload that the select ran on. The batch records which form its last result has, so every case below is
+"""A result of the one-launch top-1 select that is kept per lane (launch_small_select and kg_result_keys /
+kg_result_status in kg_runtime.cpp, LaneResult in kg_small.h). A kg_eval_select on the batch's own tables keeps one key
+and one status word per lane; the two readers copy those and expand the rows on the host through the row -> lane
+table of the upload that the select ran on. Since the form without a finisher became the default, the selects below
+run k_select_small's SMALL_ACC form (the accumulators are the result, the reader folds the replicas); the finisher's
+SMALL_LANES form, which this file was written for, is compared with it on every select of test_small_acc_results.py
+(select_acc, KG_SMALL_FINISHER=1). The batch records which form its last result has, so every case below is
 about one of: a row that reads the wrong lane, a lane that was not stored, a form flag that outlives its select, or a
 table that is not the select's.
 
@@ -81,8 +84,9 @@ def read(snap, batch, k=1):
 
 
 def select4(snap, batch, monkeypatch, want):
-    """(keys, status) of the default (lane) form under the caller's environment, after the same select on the general
-    path and in the row form: all three agree, and the keys are the oracle's (want)."""
+    """(keys, status) of the default form under the caller's environment (a result per lane: SMALL_ACC, the
+    accumulators folded by the reader), after the same select on the general path and in the row form (SMALL_ROWS4 /
+    SMALL_ROWS): all three agree, and the keys are the oracle's (want)."""
     monkeypatch.setenv("KG_NO_SMALL_SELECT", "1")
     keys0, status0 = read(snap, batch)
     monkeypatch.delenv("KG_NO_SMALL_SELECT")
